@@ -11,7 +11,14 @@ Weak scaling: every rank trains B=50 per step on its own shard of a synthetic
 MNIST-shaped dataset resident in HBM; gradients are all-reduced over RCCL/xGMI every
 step (synchronous DP), so ``value`` is the whole-job samples/s.
 
-Usage:  python bench.py [--gpus N] [--steps K] [--warmup W]
+Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+        A plain run sets up, warms up, times the K steps and prints one JSON line.
+        --dump-outputs DIR  writes what the last timed step left (parameters, optimizer
+                            slots, BatchNorm buffers, loss / correct of the timed steps) as
+                            DIR/<name>.npy, float32; inputs are seeded, so two builds run
+                            with the same arguments can be compared array for array
+        --full              also times the same K steps through the graph sizes training
+                            uses (``ms_per_step_training_graphs``)
         (N>1: bench.py starts ``torch.distributed.run --nproc-per-node N`` on itself as a
         child process; under an outer torchrun WORLD_SIZE must equal N)
 
@@ -139,6 +146,45 @@ def bench_packed(args) -> int:
     return 0
 
 
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000     # --dump-outputs writes at most this much in all
+
+
+def _collect_outputs(eng, steps):
+    """What a caller of the timed path holds after its last step, as CPU tensors: the flat
+    parameters, the optimizer slots, the BatchNorm buffers, and the loss / correct count of
+    the last ``min(steps, ring)`` timed steps in step order (last entry = last step).  Taken
+    right after the timed loop, before anything else touches the model state."""
+    import torch
+    from cloud_server_amd.runtime.engine import RING
+    eng.sync_device()
+    n = max(1, min(steps, RING, eng.host_step))
+    pos = torch.tensor([(eng.host_step - n + i) % RING for i in range(n)], device=eng.device)
+    out = {
+        "params": eng.flat,
+        "optimizer_slots": eng.slots,
+        "loss": eng.ring_loss.index_select(0, pos),
+        "correct": eng.ring_correct.index_select(0, pos),
+    }
+    bufs = [b.detach().reshape(-1).float() for b in eng.model.buffers()]
+    if bufs:
+        out["buffers"] = torch.cat(bufs)
+    return {k: v.detach().to("cpu", torch.float32).clone() for k, v in out.items()}
+
+
+def _write_outputs(outputs, dirpath) -> None:
+    """``dirpath/<name>.npy`` (float32).  An array over its share of the 64 MB budget is
+    written as a fixed, seeded sample of its flattened elements (same indices every run)."""
+    import numpy as np
+    os.makedirs(dirpath, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // (4 * max(len(outputs), 1))      # elements per array
+    for name, t in outputs.items():
+        a = np.ascontiguousarray(t.numpy(), dtype=np.float32)
+        if a.size > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=share, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirpath, name + ".npy"), a)
+
+
 def _free_port() -> int:
     import socket
     s = socket.socket()
@@ -196,8 +242,14 @@ def main() -> int:
     ap.add_argument("--optimizer", default="AdagradOptimizer")
     ap.add_argument("--jobs", type=int, default=1, help="independent jobs packed on one GPU")
     ap.add_argument("--pack", default="graph", choices=["graph", "procs"])
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step computed as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements (ms_per_step_training_graphs)")
     args = ap.parse_args()
     if args.jobs > 1:
+        if args.dump_outputs:
+            ap.error("--dump-outputs covers the single-job path (--jobs 1)")
         return bench_packed(args)
     rc = _launch_ranks(args)
     if rc is not None:
@@ -242,10 +294,12 @@ def main() -> int:
     eng.sync_device()
     dt = time.perf_counter() - t0
     dt = all_reduce_max(ctx, dt)
+    # the timed path's outputs, copied to the host before --full's second pass moves the model on
+    outputs = _collect_outputs(eng, args.steps) if args.dump_outputs and ctx.rank == 0 else None
     dt_train = None
-    if eng.extra_group_sizes:
+    if args.full and eng.extra_group_sizes:
         # the same K steps again through the graph sizes training's run_steps uses (32, 16,
-        # .., 2: no K-step graph) — reported beside the headline
+        # .., 2: no K-step graph) — reported beside the headline with --full
         eng.extra_group_sizes = []
         barrier(ctx)
         eng.sync_device()
@@ -259,6 +313,8 @@ def main() -> int:
     # run: fail loudly (agreed by every rank under data parallelism)
     eng.check_health()
     m = eng.metrics_since(eng.host_step - min(args.steps, 100))
+    if outputs is not None:
+        _write_outputs(outputs, args.dump_outputs)
 
     total = args.batch * ctx.world * args.steps / dt
     pg = "none"
@@ -274,7 +330,8 @@ def main() -> int:
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": round(dt * 1e3 / args.steps, 5),
-            # the same K steps replayed as training's graph sizes (null: K > 64, already so)
+            # --full: the same K steps replayed as training's graph sizes (null: not run, or
+            # K > 64 where the timed loop already uses them)
             "ms_per_step_training_graphs": None if dt_train is None else round(dt_train * 1e3 / args.steps, 5),
             "higher_is_better": True,
             "scaling": "weak",

@@ -131,6 +131,47 @@ def test_bench_world_size_mismatch_fails():
 import pytest  # noqa: E402
 
 
+def _bench_1gpu(*extra):
+    env = {k: v for k, v in os.environ.items()
+           if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    env["OMP_NUM_THREADS"] = "2"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3",
+           "--warmup", "1", "--batch", "8", *extra]
+    out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout
+    return json.loads(lines[0])
+
+
+def test_bench_plain_run_dumps_outputs_and_full_adds_the_second_pass(tmp_path):
+    """A plain run times its K steps only (``ms_per_step_training_graphs`` is null) and
+    ``--dump-outputs DIR`` writes the last timed step's state as float32 ``.npy`` files,
+    under 64 MB in all.  ``--full`` adds the second pass; its dump is taken before that
+    pass, so with the same arguments both runs write the same arrays (seeded inputs)."""
+    import numpy as np
+    a, b = tmp_path / "a", tmp_path / "b"
+    plain = _bench_1gpu("--dump-outputs", str(a))
+    full = _bench_1gpu("--dump-outputs", str(b), "--full")
+    for d in (plain, full):
+        assert d["metric"] == "train_samples_per_s" and d["unit"] == "samples/s"
+        assert d["higher_is_better"] is True and d["dtype"] == "fp32"
+        assert d["steps"] == 3 and d["ms_per_step"] > 0
+        assert abs(d["value"] - 8 * 1e3 / d["ms_per_step"]) <= 0.01 * d["value"]
+    assert plain["ms_per_step_training_graphs"] is None
+    assert full["ms_per_step_training_graphs"] > 0
+    names = sorted(p.name for p in a.iterdir())
+    assert names == sorted(p.name for p in b.iterdir())
+    assert {"params.npy", "optimizer_slots.npy", "loss.npy", "correct.npy"} <= set(names)
+    assert sum(p.stat().st_size for p in a.iterdir()) <= 64 * 1000 * 1000
+    for n in names:
+        x, y = np.load(a / n), np.load(b / n)
+        assert x.dtype == np.float32 and x.shape == y.shape and np.isfinite(x).all(), n
+        # the same program on the same seeded inputs: fp32 sums may only reorder
+        np.testing.assert_allclose(x, y, rtol=1e-5, atol=1e-6, err_msg=n)
+    assert np.load(a / "params.npy").size >= 2276218 and np.load(a / "loss.npy").shape == (3,)
+
+
 @pytest.mark.gpu
 def test_bench_gpus2_rehearsal_on_one_gpu():
     """The driver's N-GPU bench path on the GPU box: ``bench.py --gpus 2`` (it starts
