@@ -143,6 +143,7 @@ class Unit:
 
 class HipProgram:
     WGRAD_STRIPES = int(os.environ.get("CSA_WGRAD_STRIPES", "16"))   # (A/B knob; <= 16: the tail's loads)
+    FWD_ZERO_MAX = 4          # the pair forward's zero list (conv_pair.hip CP_MAXZ)
 
     def __init__(self, eng, forward_only: bool = False):
         """``forward_only``: the serving program (``serve.hip_infer``) — the same forward
@@ -720,7 +721,10 @@ class HipProgram:
         ys = [u.y.view(-1) for u in self.units if u.kind == "dense" and u.splits_fwd > 1]
         regions = self.zero_regions + self.zero_early
         ptrs = {t.data_ptr() for t in slabs} | {t.data_ptr() for t in ys}
-        if any(r.data_ptr() not in ptrs for r in regions) or len(slabs) > 4 or len(ys) > 4:
+        # (the pair forward's zero list holds FWD_ZERO_MAX entries and one of them is the
+        # tail's tickets: more split-K outputs than the rest keep the optimizer launch)
+        if (any(r.data_ptr() not in ptrs for r in regions) or len(slabs) > 4
+                or len(ys) + 1 > self.FWD_ZERO_MAX):
             return
         if any(t.numel() % 4 or t.data_ptr() % 16 for t in ys):
             return
@@ -742,6 +746,7 @@ class HipProgram:
         # the tickets are zeroed by the NEXT step's pair forward (no closing reset counter in
         # the carrier's tail: conv_pair.hip cp_tail_body)
         self.fwd_zero.append(self.tail_tk)
+        assert len(self.fwd_zero) <= self.FWD_ZERO_MAX
         self.tail_err = torch.zeros(1, dtype=torch.int32, device=e.device)
         self.tail_force = torch.zeros(1, dtype=torch.int32, device=e.device)   # debug: arm_tail_timeout
         # the parameter workgroups' table (one entry per 256 elements of a parameter)
