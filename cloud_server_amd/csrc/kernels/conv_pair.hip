@@ -10,14 +10,17 @@
 //            gathered (uint8, /255) into LDS, conv A is evaluated into an LDS tile
 //            (with conv B's zero padding materialised), conv B + act + 2x2 max-pool run
 //            on it, the pooled output, argmax and the following BatchNorm's partial
-//            statistics are written.  c1 never leaves the CU.
+//            statistics are written.  c1 feeds conv B from LDS; the VALU forward also
+//            stores the band's tile for the backward of a training step (c1 reuse, round 7).
 //   backward ONE launch: per band, BatchNorm backward + act backward + pool routing of
 //            the band's (and one halo row's) output gradient into an LDS dc2 tile, c1
-//            recomputed from the input rows (40 MACs per value: cheaper than storing
-//            it), conv B's weight gradient, conv B's input gradient dc1 (through act A),
+//            loaded with the prologue's loads from the tile the VALU forward stored (or
+//            recomputed from the input rows: the MFMA-forward family, CSA_PAIR_C1=0 —
+//            a K = 4 GEMM phase of ~2 us in a latency chain, profiles/r7_notes.md),
+//            conv B's weight gradient, conv B's input gradient dc1 (through act A),
 //            conv A's weight gradient — all from LDS; the weight gradients leave the
 //            launch as one atomic add per (workgroup, weight) into S stripes that the
-//            optimizer folds.  No dc2 / dc1 / c1 tensor is ever written.
+//            optimizer folds.  No dc2 / dc1 tensor is ever written.
 //
 // Family: stride-1 convs, kernels <= 5x5 (SAME / VALID), C0 <= 4, C1 <= 32 (even),
 // C2 <= 64 (multiple of 4), optional 2x2 stride-2 unpadded pool, H, W <= 64, first layer
@@ -52,6 +55,7 @@ struct CPGeom {
   int pool;                        // 2x2 / stride 2 max-pool after conv B (+ act B)
   int PH, PW;                      // unit output (pooled) size
   int PR, nbands;                  // pooled rows per band
+  int c1r;                         // backward, set by the host: launch the C1R kernels (c1 loaded, CPBwdArgs::c1)
 };
 
 struct CPFwdArgs {
@@ -400,7 +404,7 @@ __device__ __forceinline__ void cp_tables_a(const CPGeom& g, const CPBand& t, in
       o = (i * t.TXW + j) * g.C0 + c0;
     }
     offA[k] = o;
-    offPA[k] = k * 16;
+    if (offPA) offPA[k] = k * 16;
   }
 }
 
@@ -538,6 +542,7 @@ struct CPBwdArgs {
   const int* tabs; int tab_stride;  // per-band index tables (csa_conv_pair_bwd_tables) or null
   unsigned* img_tk;                 // tail: +1 per workgroup once its image tile is in LDS (or null)
   const float* bn_tab;              // [mean | rstd | a | b][C2] the step's bn_act_apply wrote, or null
+  const float* c1; int c1_stride;   // band tiles [B * nbands][c1_stride] the VALU forward stored (g.c1r)
 };
 
 // LDS carve of the backward (float offsets), shared by the kernel and the host size check.
@@ -551,7 +556,8 @@ struct CPBwdLayout {
                                     // large enough (dead by then), else after the bias sums
 };
 
-__host__ __device__ inline CPBwdLayout cp_bwd_layout(const CPGeom& g, int band, int TXH, int TXW, int T1H, int T1W) {
+__host__ __device__ inline CPBwdLayout cp_bwd_layout(const CPGeom& g, int band, int TXH, int TXW, int T1H, int T1W,
+                                                     bool c1r = false) {
   CPBwdLayout L;
   const int pr0 = band * g.PR, pr1 = min(g.PH, pr0 + g.PR);
   const bool last = band == g.nbands - 1;
@@ -569,7 +575,7 @@ __host__ __device__ inline CPBwdLayout cp_bwd_layout(const CPGeom& g, int band, 
   L.npix2 = (L.o2b - L.o2a) * g.W2; L.kp2 = (L.npix2 + 3) & ~3;
   L.npix1 = (L.o1b - L.o1a) * g.W1; L.kp1 = (L.npix1 + 3) & ~3;
   int o = 0;
-  L.pA = o; o += L.kpadA * 16;                        // conv A weight panel [kpadA][16]
+  L.pA = o; o += c1r ? 0 : L.kpadA * 16;              // conv A weight panel [kpadA][16] (recompute)
   L.pB = o; o += L.kpadB * L.c16;                     // conv B weights (HWIO, dense) + pad
   L.x = o; o += (TXH * TXW * g.C0 + 3) & ~3;
   L.c1 = o; o += (T1H * T1W * g.C1 + 3) & ~3;
@@ -586,7 +592,7 @@ __host__ __device__ inline CPBwdLayout cp_bwd_layout(const CPGeom& g, int band, 
   const int rsz = rmain + (rA_in_dc2 ? 0 : 4 * 16 * 16);
   L.red = o; o += ((rsz > 8 * CP_MAXC2 ? rsz : 8 * CP_MAXC2) + 3) & ~3;
   L.rA = rA_in_dc2 ? L.dc2 : L.red + rmain;
-  L.offs = o; o += 2 * L.kpadA + L.kp2 * 2 + L.kpadD * 2 + L.kp1 * 2 + L.n16b + 16;
+  L.offs = o; o += (c1r ? 1 : 2) * L.kpadA + L.kp2 * 2 + L.kpadD * 2 + L.kp1 * 2 + L.n16b + 16;
   L.end = o;
   (void)L.wA;
   return L;
@@ -595,15 +601,18 @@ __host__ __device__ inline CPBwdLayout cp_bwd_layout(const CPGeom& g, int band, 
 // The backward's per-band index tables (they depend on the band only): into the int region
 // at s_offA (layout: see cp_bwd_body).  Computed once per geometry into global memory by
 // cp_bwd_tables_kernel, or by every workgroup when no table buffer was given.
-__device__ __forceinline__ void cp_bwd_tables(const CPGeom& g, const CPBand& t, const CPBwdLayout& L, int* s_offA) {
-  int* s_offPA = s_offA + L.kpadA;
-  int* s_pix2 = s_offPA + L.kpadA;
+__device__ __forceinline__ void cp_bwd_tables(const CPGeom& g, const CPBand& t, const CPBwdLayout& L, int* s_offA,
+                                              bool c1r = false) {
+  int* s_pix2 = s_offA + L.kpadA;
   int* s_pixd = s_pix2 + L.kp2;
   int* s_offD = s_pixd + L.kp2;
   int* s_offW = s_offD + L.kpadD;
   int* s_pix1x = s_offW + L.kpadD;
   int* s_pix1d = s_pix1x + L.kp1;
   int* s_tapB = s_pix1d + L.kp1;
+  // conv A's panel rows come LAST: a backward that loads c1 (c1r) neither carves nor loads
+  // them, and its region is a prefix of the recompute's
+  int* s_offPA = c1r ? nullptr : s_tapB + L.n16b + 16;
   cp_tables_a(g, t, L.kpadA, s_offA, s_offPA);
   {
     const FastDiv dw2(g.W2), dw1(g.W1);
@@ -650,6 +659,7 @@ __host__ __device__ inline int cp_bwd_tab_ints(const CPBwdLayout& L) { return L.
 // Prologue register batch of the backward (ONE = true): weights (panel A + dense wB),
 // x tile and BN slab rows per thread.  The host picks ONE when every band fits.
 constexpr int CPB_UP = 8, CPB_UX = 2, CPB_US = 8, CPB_UT = 4;
+constexpr int CPB_UC = 2;                  // float4s of the stored c1 tile per thread (c1 reuse)
 
 // The route's extent for workgroup (image b, band of L): unit rows [ua, ub) of the pair's
 // output (pooled or not) whose gradients land in the band's zero-padded dc2 tile.
@@ -667,7 +677,7 @@ __device__ __forceinline__ CPRoute cp_route(const CPGeom& g, const CPBwdLayout& 
   return r;
 }
 
-template <bool ONE>
+template <bool ONE, bool C1R>
 __device__ __forceinline__ void cp_bwd_body(const CPBwdArgs& a, const int bid, float* smem) {
   const CPGeom& g = a.g;
   const int b = bid / g.nbands, band = bid % g.nbands;
@@ -678,7 +688,12 @@ __device__ __forceinline__ void cp_bwd_body(const CPBwdArgs& a, const int bid, f
   const bool last_ = band == g.nbands - 1;
   const int o2b_ = g.pool ? (last_ ? g.H2 : 2 * min(g.PH, pr0 + g.PR)) : min(g.PH, pr0 + g.PR);
   const CPBand t = cp_band(g, o2a_, o2b_);            // c1 tile rows o2a - PTB ..
-  const CPBwdLayout L = cp_bwd_layout(g, band, t.TXH, t.TXW, t.T1H, t.T1W);
+  // c1 reuse: the tile the VALU forward stored for this (image, band) joins the prologue's
+  // batch of loads; no conv A panel, bias or panel-row table, no conv A pass.  (C1R: its own
+  // instantiation — the host launches it when g.c1r is set — so the recompute's code and
+  // registers stay out of it, and it out of the recompute's)
+  constexpr bool c1r = ONE && C1R;
+  const CPBwdLayout L = cp_bwd_layout(g, band, t.TXH, t.TXW, t.T1H, t.T1W, c1r);
   float* s_pA = smem + L.pA;
   float* s_wB = smem + L.pB;
   float* s_x = smem + L.x;
@@ -690,22 +705,24 @@ __device__ __forceinline__ void cp_bwd_body(const CPBwdArgs& a, const int bid, f
   // is written only after the route, their last reader) — no static LDS in this launch
   float* s_bn = s_red + 2 * CP_MAXC2;                        // [4][MAXC2] mean | rstd | a | b
   float* s_ss = s_bn + 4 * CP_MAXC2;                         // [2][C2] backward sums
-  int* s_offA = reinterpret_cast<int*>(smem + L.offs);      // conv A (recompute): x offsets
-  int* s_offPA = s_offA + L.kpadA;                           //                    panel rows
-  int* s_pix2 = s_offPA + L.kpadA;                           // dwB: pixel -> c1 tile offset
+  int* s_offA = reinterpret_cast<int*>(smem + L.offs);      // conv A / dwA: x offsets
+  int* s_pix2 = s_offA + L.kpadA;                            // dwB: pixel -> c1 tile offset
   int* s_pixd = s_pix2 + L.kp2;                              //      pixel -> dc2 tile offset
   int* s_offD = s_pixd + L.kp2;                              // dc1: k=(i,j,c2) -> dc2 offset
   int* s_offW = s_offD + L.kpadD;                            //      k -> weight offset
   int* s_pix1x = s_offW + L.kpadD;                           // dwA: pixel -> x tile offset
   int* s_pix1d = s_pix1x + L.kp1;                            //      pixel -> dc1 offset
   int* s_tapB = s_pix1d + L.kp1;                             // dwB: tap -> c1 tile offset
+  int* s_offPA = s_tapB + L.n16b + 16;                       // conv A (recompute): panel rows
   CP_STAMP(8);
   // Prologue.  ONE: every global load of the prologue — the two weight blocks, the x tile,
   // both BN slabs and the BN affine vectors — is issued first, the index tables below are
   // computed while they travel (VALU work that otherwise sat between dependent round
   // trips), then the LDS stores and the slab reduction.
-  const int nA = L.kpadA * 16, nWB = L.KB * g.C2, nP = nA + L.kpadB * L.c16;
+  const int nA = c1r ? 0 : L.kpadA * 16, nWB = L.KB * g.C2, nP = nA + L.kpadB * L.c16;
   const int nX = t.TXH * t.TXW * g.C0;
+  const int nC4 = (t.T1H * t.T1W * g.C1 + 3) >> 2;      // the c1 tile in float4s
+  float4 cv[CPB_UC];
   const int C2x2 = 2 * g.C2, sper = CP_THREADS / C2x2;
   const int scol = (int)threadIdx.x % C2x2, srow = (int)threadIdx.x / C2x2;
   const bool sact = srow < sper;
@@ -740,6 +757,15 @@ __device__ __forceinline__ void cp_bwd_body(const CPBwdArgs& a, const int bid, f
       pv[u] = 0.f;
       const float* p = !ok ? a.wA : (inA ? a.wA + k * g.C1 + n : a.wB + f);
       if (u * CP_THREADS < nP) pv[u] = *p;         // (whole batches past the panels: none)
+    }
+    if (c1r) {
+      const float4* cs = reinterpret_cast<const float4*>(a.c1 + (long)bid * a.c1_stride);
+#pragma unroll
+      for (int u = 0; u < CPB_UC; ++u) {
+        const int e = u * CP_THREADS + (int)threadIdx.x;
+        cv[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (u * CP_THREADS < nC4) cv[u] = cs[e < nC4 ? e : 0];
+      }
     }
     if (a.bn_on && a.bn_tab) {
       // the forward tables come folded (one value per thread); of the backward slab only
@@ -801,7 +827,7 @@ __device__ __forceinline__ void cp_bwd_body(const CPBwdArgs& a, const int bid, f
   CP_STAMP(16);
   for (int i = threadIdx.x; i < L.D2H * L.D2W * g.C2; i += CP_THREADS) s_dc2[i] = 0.f;
   for (int i = threadIdx.x; i < g.C1; i += CP_THREADS) s_dc1[L.npix1 * g.C1 + i] = 0.f;
-  if (!a.tabs) cp_bwd_tables(g, t, L, s_offA);
+  if (!a.tabs) cp_bwd_tables(g, t, L, s_offA, c1r);
   CP_STAMP(17);
   if (a.tabs) {
 #pragma unroll
@@ -825,6 +851,14 @@ __device__ __forceinline__ void cp_bwd_body(const CPBwdArgs& a, const int bid, f
     for (int u = 0; u < CPB_UX; ++u) {
       const int e = u * CP_THREADS + (int)threadIdx.x;
       if (e < nX) s_x[e] = xok[u] ? (float)xv[u] * (1.0f / 255.0f) : 0.f;
+    }
+    if (c1r) {
+#pragma unroll
+      for (int u = 0; u < CPB_UC; ++u) {
+        pin(cv[u].x); pin(cv[u].y); pin(cv[u].z); pin(cv[u].w);
+        const int e = u * CP_THREADS + (int)threadIdx.x;
+        if (e < nC4) reinterpret_cast<float4*>(s_c1)[e] = cv[u];
+      }
     }
   }
   CP_STAMP(18);
@@ -944,8 +978,9 @@ __device__ __forceinline__ void cp_bwd_body(const CPBwdArgs& a, const int bid, f
     }
   }
   CP_STAMP(10);
-  // ---- c1 tile (rows o2a - PTB ..) recomputed from the input rows
-  cp_conv_a(g, t, smem, s_x, s_pA, L.kpadA, s_offA, s_offPA, a.bA, a.actA, a.alphaA, s_c1);
+  // ---- c1 tile (rows o2a - PTB ..) recomputed from the input rows, unless the prologue
+  // loaded it (the barrier stays: the route's dc2 stores are read by the GEMMs below)
+  if (!c1r) cp_conv_a(g, t, smem, s_x, s_pA, L.kpadA, s_offA, s_offPA, a.bA, a.actA, a.alphaA, s_c1);
   __syncthreads();
   CP_STAMP(11);
   // ---- weight gradient B: [taps (i, j, c1)] x [C2], K = owned conv-B-output pixels
@@ -1054,10 +1089,10 @@ __device__ __forceinline__ void cp_bwd_body(const CPBwdArgs& a, const int bid, f
   CP_STAMP(15);
 }
 
-template <bool ONE>
+template <bool ONE, bool C1R>
 __global__ __launch_bounds__(CP_THREADS) void conv_pair_bwd_kernel(CPBwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  cp_bwd_body<ONE>(a, (int)blockIdx.x, smem);
+  cp_bwd_body<ONE, C1R>(a, (int)blockIdx.x, smem);
 }
 
 // Horizontal fusion (round 4): the pair backward's workgroups [0, B * nbands) followed by
@@ -1226,12 +1261,12 @@ __device__ __forceinline__ void cp_tail_body(const CPTail& t, int npair, int k) 
     __hip_atomic_store(t.force, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-template <bool ONE, int NSLOT>
+template <bool ONE, int NSLOT, bool C1R>
 __device__ __forceinline__ void cp_bwd_upd_body(const CPBwdArgs& a, const DUSegs& u, const CPTail& t, float* smem) {
   const int npair = a.g.B * a.g.nbands;
   const int bid = (int)blockIdx.x;
   if (bid < npair) {
-    cp_bwd_body<ONE>(a, bid, smem);
+    cp_bwd_body<ONE, C1R>(a, bid, smem);
     if (t.on) {
       // the barrier drains every wave's stripe atomics (device-scope: visible once done);
       // block 0's plain stores (BN parameter gradients, running statistics) get ONE
@@ -1279,11 +1314,11 @@ __constant__ long long* g_cp_life = nullptr;
 // the same for the VALU pair forward (csa_cpv_life_debug)
 __constant__ long long* g_cpv_life = nullptr;
 
-template <bool ONE, int NSLOT>
+template <bool ONE, int NSLOT, bool C1R>
 __device__ __forceinline__ void cp_bwd_upd_entry(const CPBwdArgs& a, const DUSegs& u, const CPTail& t) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   if (g_cp_life && threadIdx.x == 0) g_cp_life[2 * blockIdx.x] = (long long)__builtin_amdgcn_s_memrealtime();
-  cp_bwd_upd_body<ONE, NSLOT>(a, u, t, smem);
+  cp_bwd_upd_body<ONE, NSLOT, C1R>(a, u, t, smem);
   if (g_cp_life) {
     __syncthreads();
     if (threadIdx.x == 0) g_cp_life[2 * blockIdx.x + 1] = (long long)__builtin_amdgcn_s_memrealtime();
@@ -1295,14 +1330,14 @@ __device__ __forceinline__ void cp_bwd_upd_entry(const CPBwdArgs& a, const DUSeg
 // 0 / 1 optimizer slots; the LDS: <= 31.2 KB per workgroup (the pair's BatchNorm scratch and
 // dwA partials alias dead regions, the head epilogue reuses the Xw slice, no static LDS).
 // Two slots (Adam) would spill at 5 waves: that form keeps the compiler's choice (4).
-template <bool ONE, int NSLOT>
+template <bool ONE, int NSLOT, bool C1R>
 __global__ __launch_bounds__(CP_THREADS) __attribute__((amdgpu_waves_per_eu(5)))
 void conv_pair_bwd_upd_kernel(CPBwdArgs a, DUSegs u, CPTail t) {
-  cp_bwd_upd_entry<ONE, NSLOT>(a, u, t);
+  cp_bwd_upd_entry<ONE, NSLOT, C1R>(a, u, t);
 }
-template <bool ONE>
+template <bool ONE, bool C1R>
 __global__ __launch_bounds__(CP_THREADS) void conv_pair_bwd_upd2_kernel(CPBwdArgs a, DUSegs u, CPTail t) {
-  cp_bwd_upd_entry<ONE, 2>(a, u, t);
+  cp_bwd_upd_entry<ONE, 2, C1R>(a, u, t);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1312,7 +1347,9 @@ __global__ __launch_bounds__(CP_THREADS) void conv_pair_bwd_upd2_kernel(CPBwdArg
 // per-tile epilogues: stamps convA 2.2 us, convB+pool 3.4 us of a 12.9 us launch).  Here
 // every phase is one pass of plain FMAs over LDS with the whole workgroup busy:
 //   loads   weights of both convs, biases and the band's uint8 input rows in ONE batch
-//   conv A  one thread per c1 value of the band's tile (+ act A, zero outside the image)
+//   conv A  one thread per c1 value of the band's tile (+ act A, zero outside the image);
+//           with CPVFwdArgs::c1 the tile also goes to global memory, in the LDS tile's
+//           order (band-tile layout, zero padding included), for the backward's prologue
 //   conv B  one thread per (unit pixel, output channel): the pool window's positions
 //           (+ bias, act B, max + argmax) with every weight read once per position
 //   stats   per-channel {sum, sum^2} of the band folded in fixed order, one row per band
@@ -1330,6 +1367,7 @@ struct CPVFwdArgs {
   const float* wA; const float* bA; int actA; float alphaA;
   const float* wB; const float* bB; int actB; float alphaB;
   float* y; uint8_t* argmax; float* stat; int nslab;
+  float* c1; int c1_stride;        // band tiles [B * nbands][c1_stride] kept for the backward, or null
 };
 
 __host__ __device__ inline int cpv_txw(const CPGeom& g) { return g.W2 + g.KBw - 1 + g.KAw - 1; }
@@ -1413,24 +1451,34 @@ __global__ __launch_bounds__(CPV_T) void cpv_fwd_kernel(CPVFwdArgs a, CPZero z, 
     int koff[CPV_MAXKA];
 #pragma unroll
     for (int k = 0; k < CPV_MAXKA; ++k) koff[k] = k < KA ? s_koffA[k] : 0;
-    const int nc1p = g.C1 >> 1;
-    for (int it = tid; it < npx1 * nc1p; it += CPV_T) {
-      const int cp = it % nc1p, pix = it / nc1p, c1 = 2 * cp;
-      const int tx = pix % t.T1W, ty = pix / t.T1W;
-      const int yy = t.c1y0 + ty, xx = tx - g.PLB;
-      const bool in = yy >= 0 && yy < g.H1 && xx >= 0 && xx < g.W1;
-      const float* xb = s_x + (ty * t.TXW + tx) * g.C0;
-      float a0 = s_b[c1], a1 = s_b[c1 + 1];
+    const int nc1p = g.C1 >> 1, nit = npx1 * nc1p;
+    // the tile also goes out for the backward (a.c1: band-tile layout, the LDS tile's own
+    // order with its zero padding, so the backward's load is one contiguous copy); the
+    // stores drain under conv B.  Past the tile, up to the stride: zeros (the backward's
+    // last band is one row taller when H2 is odd — a row only zero gradients meet)
+    float* gc1 = a.c1 ? a.c1 + (long)blockIdx.x * a.c1_stride : nullptr;
+    const int nst = gc1 ? max(nit, a.c1_stride >> 1) : nit;     // (host: stride >= every band's tile)
+    for (int it = tid; it < nst; it += CPV_T) {
+      float2 v = make_float2(0.f, 0.f);
+      if (it < nit) {
+        const int cp = it % nc1p, pix = it / nc1p, c1 = 2 * cp;
+        const int tx = pix % t.T1W, ty = pix / t.T1W;
+        const int yy = t.c1y0 + ty, xx = tx - g.PLB;
+        const bool in = yy >= 0 && yy < g.H1 && xx >= 0 && xx < g.W1;
+        const float* xb = s_x + (ty * t.TXW + tx) * g.C0;
+        float a0 = s_b[c1], a1 = s_b[c1 + 1];
 #pragma unroll
-      for (int k = 0; k < CPV_MAXKA; ++k) {
-        if (k >= KA) break;                                 // uniform
-        const float xv = xb[koff[k]];
-        const float2 w = *reinterpret_cast<const float2*>(s_w + k * g.C1 + c1);
-        a0 = fmaf(xv, w.x, a0);
-        a1 = fmaf(xv, w.y, a1);
+        for (int k = 0; k < CPV_MAXKA; ++k) {
+          if (k >= KA) break;                                 // uniform
+          const float xv = xb[koff[k]];
+          const float2 w = *reinterpret_cast<const float2*>(s_w + k * g.C1 + c1);
+          a0 = fmaf(xv, w.x, a0);
+          a1 = fmaf(xv, w.y, a1);
+        }
+        if (in) v = make_float2(act_fwd(a0, a.actA, a.alphaA), act_fwd(a1, a.actA, a.alphaA));
+        *reinterpret_cast<float2*>(s_c1 + pix * g.C1 + c1) = v;
       }
-      *reinterpret_cast<float2*>(s_c1 + pix * g.C1 + c1) =
-          in ? make_float2(act_fwd(a0, a.actA, a.alphaA), act_fwd(a1, a.actA, a.alphaA)) : make_float2(0.f, 0.f);
+      if (gc1) out_store2(gc1 + 2 * it, v.x, v.y);
     }
   }
   __syncthreads();
@@ -1965,7 +2013,7 @@ static bool cp_bwd_one_batch(const CPBwdArgs& a) {
     const int r2a = g.pool ? 2 * pr0 : pr0, r2b = g.pool ? (last ? g.H2 : 2 * pr1) : pr1;
     const int T1H = (r2b - r2a) + g.KBh - 1, T1W = g.W2 + g.KBw - 1;
     const int TXH = T1H + g.KAh - 1, TXW = T1W + g.KAw - 1;
-    const CPBwdLayout L = cp_bwd_layout(g, band, TXH, TXW, T1H, T1W);
+    const CPBwdLayout L = cp_bwd_layout(g, band, TXH, TXW, T1H, T1W, g.c1r != 0);
     if (L.kpadA * 16 + L.kpadB * L.c16 > CPB_UP * CP_THREADS || TXH * TXW * g.C0 > CPB_UX * CP_THREADS ||
         g.C1 > 16)
       return false;
@@ -1984,7 +2032,7 @@ static size_t cp_lds(const CPGeom& g, bool bwd) {
     const int TXH = T1H + g.KAh - 1, TXW = T1W + g.KAw - 1;
     size_t f;
     if (bwd) {
-      f = cp_bwd_layout(g, band, TXH, TXW, T1H, T1W).end;
+      f = cp_bwd_layout(g, band, TXH, TXW, T1H, T1W, g.c1r != 0).end;
     } else {
       const int KA = g.KAh * g.KAw * g.C0, KB = g.KBh * g.KBw * g.C1;
       const int kpadA = (KA + 3) & ~3, kpadB = (KB + 3) & ~3, c16 = (g.C2 + 15) & ~15;
@@ -1997,9 +2045,62 @@ static size_t cp_lds(const CPGeom& g, bool bwd) {
   return mx * sizeof(float);
 }
 
+// c1 reuse: floats of one (image, band) tile of the buffer the VALU forward stores and the
+// one-batch MFMA backward loads — the tallest band's backward tile, a whole number of
+// float4s.  0: the geometry keeps the recompute (no VALU forward, or a tile beyond the
+// backward's register batch).
+static int cp_c1_stride(const CPGeom& g) {
+  if (!cpv_ok(g)) return 0;
+  int m = 0;
+  for (int band = 0; band < g.nbands; ++band) {
+    const int pr0 = band * g.PR;
+    const bool last = band == g.nbands - 1;
+    const int o2a = g.pool ? 2 * pr0 : pr0;
+    const int o2b = g.pool ? (last ? g.H2 : 2 * std::min(g.PH, pr0 + g.PR)) : std::min(g.PH, pr0 + g.PR);
+    const CPBand t = cp_band(g, o2a, o2b);
+    m = std::max(m, t.T1H * t.T1W * g.C1);
+  }
+  m = (m + 3) & ~3;
+  return m > 4 * CPB_UC * CP_THREADS ? 0 : m;
+}
+
 }  // namespace csa
 
 using namespace csa;
+
+// c1 reuse: the buffer ([B * nbands][stride] floats, 16-byte aligned) the NEXT
+// csa_conv_pair_fwd stores its conv-A tiles into / the NEXT csa_conv_pair_bwd loads them
+// from instead of recomputing conv A (host state consumed by that call, like the BatchNorm
+// tables).  csa_conv_pair_c1_size: floats to allocate, 0 when the geometry keeps the
+// recompute.  csa_conv_pair_c1_bands: {c1 row of tile row 0, tile rows, tile columns, stride}
+// per band (the column of tile column 0 is -PLB).
+static thread_local float* g_cp_c1_fwd = nullptr;
+static thread_local long g_cp_c1_fwd_n = 0;
+static thread_local const float* g_cp_c1_bwd = nullptr;
+static thread_local long g_cp_c1_bwd_n = 0;
+CSA_API void csa_conv_pair_c1_fwd(float* c1, long n) { g_cp_c1_fwd = c1; g_cp_c1_fwd_n = n; }
+CSA_API void csa_conv_pair_c1_bwd(const float* c1, long n) { g_cp_c1_bwd = c1; g_cp_c1_bwd_n = n; }
+
+CSA_API long csa_conv_pair_c1_size(const int* geom) {
+  CPGeom g;
+  if (!cp_geom(geom, g)) return -1;
+  return (long)cp_c1_stride(g) * g.B * g.nbands;
+}
+
+CSA_API int csa_conv_pair_c1_bands(const int* geom, int* out, int cap) {
+  CPGeom g;
+  if (!cp_geom(geom, g) || !out || cap < g.nbands) return -1;
+  const int stride = cp_c1_stride(g);
+  for (int band = 0; band < g.nbands; ++band) {
+    const int pr0 = band * g.PR;
+    const bool last = band == g.nbands - 1;
+    const int o2a = g.pool ? 2 * pr0 : pr0;
+    const int o2b = g.pool ? (last ? g.H2 : 2 * std::min(g.PH, pr0 + g.PR)) : std::min(g.PH, pr0 + g.PR);
+    const CPBand t = cp_band(g, o2a, o2b);
+    out[4 * band] = t.c1y0; out[4 * band + 1] = t.T1H; out[4 * band + 2] = t.T1W; out[4 * band + 3] = stride;
+  }
+  return g.nbands;
+}
 
 CSA_API int csa_cp_debug(long long* p) {
   return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_cp_dbg), &p, sizeof(p));
@@ -2104,13 +2205,22 @@ CSA_API int csa_conv_pair_fwd(const int* geom, const uint8_t* img, const int64_t
   z.n = nzero;
   const CPOptCarry oc = g_cp_carry;
   g_cp_carry = CPOptCarry{};
+  float* c1 = g_cp_c1_fwd;                           // consumed by this call, whatever it returns
+  const long c1n = g_cp_c1_fwd_n;
+  g_cp_c1_fwd = nullptr;
   CPFwdArgs a{};
   if (!cp_geom(geom, a.g) || cp_lds(a.g, false) > CP_LDS_MAX) return -1;
   a.img = img; a.idx = idx; a.cursor = cursor; a.wA = wA; a.bA = bA; a.actA = actA; a.alphaA = alphaA;
   a.wB = wB; a.bB = bB; a.actB = actB; a.alphaB = alphaB; a.y = y; a.argmax = argmax; a.stat = stat;
   a.nslab = nslab < 1 ? 1 : nslab;
   if (cpv_ok(a.g)) {
-    CPVFwdArgs v{a.g, img, idx, cursor, wA, bA, actA, alphaA, wB, bB, actB, alphaB, y, argmax, stat, a.nslab};
+    CPVFwdArgs v{a.g, img, idx, cursor, wA, bA, actA, alphaA, wB, bB, actB, alphaB, y, argmax, stat, a.nslab,
+                 nullptr, 0};
+    if (c1) {
+      const int stride = cp_c1_stride(a.g);
+      if (!stride || ((uintptr_t)c1 & 15) || c1n < (long)stride * a.g.B * a.g.nbands) return -8;
+      v.c1 = c1; v.c1_stride = stride;
+    }
     const unsigned grid = (unsigned)(a.g.B * a.g.nbands + oc.blocks);
     if (oc.blocks) {
       if (a.g.KBh == 2) hipLaunchKernelGGL((cpv_fwd_kernel<2, 2, true>), dim3(grid), dim3(CPV_T), cpv_fwd_lds(a.g), st, v, z, oc);
@@ -2122,6 +2232,7 @@ CSA_API int csa_conv_pair_fwd(const int* geom, const uint8_t* img, const int64_t
     return (int)hipGetLastError();
   }
   if (oc.blocks) return -7;                        // only the VALU forward carries the update
+  if (c1) return -8;                               // only the VALU forward stores c1
   static bool attr = hipFuncSetAttribute((const void*)conv_pair_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                          (int)CP_LDS_MAX) == hipSuccess;
   if (!attr) return -3;
@@ -2134,17 +2245,17 @@ CSA_API int csa_conv_pair_fwd(const int* geom, const uint8_t* img, const int64_t
 // deferred dense segments: host state consumed by that launch.
 static thread_local CPTail g_cp_tail{};
 
-template <bool ONE, int NSLOT>
+template <bool ONE, int NSLOT, bool C1R>
 static int cp_launch_bwd_upd_t(const CPBwdArgs& a, const DUSegs& u, const CPTail& t, size_t lds, hipStream_t st) {
-  const void* fn = NSLOT == 2 ? (const void*)conv_pair_bwd_upd2_kernel<ONE>
-                              : (const void*)conv_pair_bwd_upd_kernel<ONE, NSLOT < 2 ? NSLOT : 0>;
+  const void* fn = NSLOT == 2 ? (const void*)conv_pair_bwd_upd2_kernel<ONE, C1R>
+                              : (const void*)conv_pair_bwd_upd_kernel<ONE, NSLOT < 2 ? NSLOT : 0, C1R>;
   static const bool attr = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CP_LDS_MAX) == hipSuccess;
   if (!attr) return -3;
   const unsigned blocks = (unsigned)(a.g.B * a.g.nbands + u.start[u.nseg] + (t.on ? t.param_blocks + t.stage_blocks : 0));
   if constexpr (NSLOT == 2)
-    hipLaunchKernelGGL((conv_pair_bwd_upd2_kernel<ONE>), dim3(blocks), dim3(CP_THREADS), lds, st, a, u, t);
+    hipLaunchKernelGGL((conv_pair_bwd_upd2_kernel<ONE, C1R>), dim3(blocks), dim3(CP_THREADS), lds, st, a, u, t);
   else
-    hipLaunchKernelGGL((conv_pair_bwd_upd_kernel<ONE, NSLOT>), dim3(blocks), dim3(CP_THREADS), lds, st, a, u, t);
+    hipLaunchKernelGGL((conv_pair_bwd_upd_kernel<ONE, NSLOT, C1R>), dim3(blocks), dim3(CP_THREADS), lds, st, a, u, t);
   return (int)hipGetLastError();
 }
 
@@ -2161,9 +2272,14 @@ static int cp_launch_bwd_upd(CPBwdArgs a, const DUSegs& u, hipStream_t st) {
   if (dl > lds) lds = dl;
   const int ns = opt_nslots(u.seg[0].opt);
   const bool one = cp_bwd_one_batch(a);
-  if (ns == 0) return one ? cp_launch_bwd_upd_t<true, 0>(a, u, t, lds, st) : cp_launch_bwd_upd_t<false, 0>(a, u, t, lds, st);
-  if (ns == 1) return one ? cp_launch_bwd_upd_t<true, 1>(a, u, t, lds, st) : cp_launch_bwd_upd_t<false, 1>(a, u, t, lds, st);
-  return one ? cp_launch_bwd_upd_t<true, 2>(a, u, t, lds, st) : cp_launch_bwd_upd_t<false, 2>(a, u, t, lds, st);
+  if (a.g.c1r) {                                   // (set only for a one-batch prologue)
+    if (ns == 0) return cp_launch_bwd_upd_t<true, 0, true>(a, u, t, lds, st);
+    if (ns == 1) return cp_launch_bwd_upd_t<true, 1, true>(a, u, t, lds, st);
+    return cp_launch_bwd_upd_t<true, 2, true>(a, u, t, lds, st);
+  }
+  if (ns == 0) return one ? cp_launch_bwd_upd_t<true, 0, false>(a, u, t, lds, st) : cp_launch_bwd_upd_t<false, 0, false>(a, u, t, lds, st);
+  if (ns == 1) return one ? cp_launch_bwd_upd_t<true, 1, false>(a, u, t, lds, st) : cp_launch_bwd_upd_t<false, 1, false>(a, u, t, lds, st);
+  return one ? cp_launch_bwd_upd_t<true, 2, false>(a, u, t, lds, st) : cp_launch_bwd_upd_t<false, 2, false>(a, u, t, lds, st);
 }
 
 // Tail plan: the parameter table of the tail's parameter workgroups, written to the device
@@ -2290,6 +2406,9 @@ CSA_API int csa_conv_pair_bwd(const int* geom, const uint8_t* img, const int64_t
   CPBwdArgs a{};
   const float* bn_tab = g_cp_bn_tab;                 // consumed by this call, whatever it returns
   g_cp_bn_tab = nullptr;
+  const float* c1 = g_cp_c1_bwd;
+  const long c1n = g_cp_c1_bwd_n;
+  g_cp_c1_bwd = nullptr;
   if (!cp_geom(geom, a.g) || cp_lds(a.g, true) > CP_LDS_MAX) return -1;
   a.tabs = tabs;
   a.tab_stride = tabs ? cp_bwd_tab_stride(a.g) : 0;
@@ -2301,9 +2420,11 @@ CSA_API int csa_conv_pair_bwd(const int* geom, const uint8_t* img, const int64_t
   a.bn_tab = a.bn_on ? bn_tab : nullptr;
   a.dscale = dscale; a.doffset = doffset; a.run_mean = run_mean; a.run_var = run_var; a.momentum = momentum;
   a.dwA = dwA; a.dbA = dbA; a.dwB = dwB; a.dbB = dbB; a.stripes = stripes < 1 ? 1 : stripes;
-  static bool attr = hipFuncSetAttribute((const void*)conv_pair_bwd_kernel<true>,
+  static bool attr = hipFuncSetAttribute((const void*)conv_pair_bwd_kernel<true, false>,
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)CP_LDS_MAX) == hipSuccess &&
-                     hipFuncSetAttribute((const void*)conv_pair_bwd_kernel<false>,
+                     hipFuncSetAttribute((const void*)conv_pair_bwd_kernel<true, true>,
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)CP_LDS_MAX) == hipSuccess &&
+                     hipFuncSetAttribute((const void*)conv_pair_bwd_kernel<false, false>,
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)CP_LDS_MAX) == hipSuccess;
   if (!attr) return -3;
   const dim3 grid((unsigned)(a.g.B * a.g.nbands));
@@ -2316,6 +2437,7 @@ CSA_API int csa_conv_pair_bwd(const int* geom, const uint8_t* img, const int64_t
                         hipFuncSetAttribute((const void*)cpv_bwd_kernel<3, 3>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                             (int)CP_LDS_MAX) == hipSuccess;
     if (!vattr) return -3;
+    if (c1) return -8;                                          // only the MFMA backward loads c1
     if (a.g.KBh == 2) hipLaunchKernelGGL((cpv_bwd_kernel<2, 2>), grid, dim3(CPV_T), cpv_bwd_lds_max(a.g), st, a);
     else hipLaunchKernelGGL((cpv_bwd_kernel<3, 3>), grid, dim3(CPV_T), cpv_bwd_lds_max(a.g), st, a);
     if (g_cp_tail.on) return -7;                                // a tail needs the MFMA carrier
@@ -2323,12 +2445,21 @@ CSA_API int csa_conv_pair_bwd(const int* geom, const uint8_t* img, const int64_t
     if (du_take(u) > 0) return du_flush_segs(u, st);
     return (int)hipGetLastError();
   }
+  if (c1) {
+    // the tiles the VALU forward of this step stored: the one-batch prologue loads them (the
+    // table stride above is the full region's: the reuse's tables are a prefix of it)
+    const int stride = cp_c1_stride(a.g);
+    if (!stride || ((uintptr_t)c1 & 15) || c1n < (long)stride * a.g.B * a.g.nbands) return -8;
+    if (cp_bwd_one_batch(a)) { a.c1 = c1; a.c1_stride = stride; a.g.c1r = 1; }   // (else: recompute)
+  }
   DUSegs u;
   if (du_take(u) > 0) return cp_launch_bwd_upd(a, u, st);
   if (g_cp_tail.on) return -7;
-  if (cp_bwd_one_batch(a))
-    hipLaunchKernelGGL(conv_pair_bwd_kernel<true>, grid, dim3(CP_THREADS), cp_lds(a.g, true), st, a);
+  if (a.g.c1r)
+    hipLaunchKernelGGL((conv_pair_bwd_kernel<true, true>), grid, dim3(CP_THREADS), cp_lds(a.g, true), st, a);
+  else if (cp_bwd_one_batch(a))
+    hipLaunchKernelGGL((conv_pair_bwd_kernel<true, false>), grid, dim3(CP_THREADS), cp_lds(a.g, true), st, a);
   else
-    hipLaunchKernelGGL(conv_pair_bwd_kernel<false>, grid, dim3(CP_THREADS), cp_lds(a.g, true), st, a);
+    hipLaunchKernelGGL((conv_pair_bwd_kernel<false, false>), grid, dim3(CP_THREADS), cp_lds(a.g, true), st, a);
   return (int)hipGetLastError();
 }

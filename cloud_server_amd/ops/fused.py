@@ -97,6 +97,10 @@ _SIGS = {
     "csa_dd_group_end": (I, [P]),
     "csa_cp_du_debug": (I, [P]),
     "csa_conv_pair_bn_tab": (None, [P]),
+    "csa_conv_pair_c1_size": (L, [P]),
+    "csa_conv_pair_c1_bands": (I, [P, P, I]),
+    "csa_conv_pair_c1_fwd": (None, [P, L]),
+    "csa_conv_pair_c1_bwd": (None, [P, L]),
     "csa_head_debug": (I, [P]),
     "csa_conv_pair_fwd": (I, [P, P, P, P, P, P, I, F, P, P, I, F, P, P, P, I, P, P, I, P]),
     "csa_conv_pair_fwd_carry": (I, [I, F, P, P, P, P, P, P, I, P, P, I]),

@@ -568,8 +568,10 @@ class HipProgram:
     # ------------------------------------------------------------------ conv pair
     def _plan_pair(self) -> None:
         """``conv [act] conv [act] [pool]`` on the raw images (the sample's conv1 -> conv2
-        -> pool) runs as ONE forward and ONE backward launch (conv_pair.hip): c1 stays in
-        LDS, the backward recomputes it and never writes dc2 / dc1."""
+        -> pool) runs as ONE forward and ONE backward launch (conv_pair.hip): dc2 / dc1 are
+        never written.  c1: the VALU forward stores its band tiles (``pair_c1``, allocated by
+        ``_alloc``) and the backward loads them in its prologue; the MFMA-forward family,
+        deterministic mode and ``CSA_PAIR_C1=0`` keep c1 in LDS and recompute it."""
         self.pair = None
         if len(self.units) < 2:
             return
@@ -1090,6 +1092,16 @@ class HipProgram:
             self.head_kw = K * 10
             self.head_mloss = torch.zeros(G, **f32)
             self.head_mcorr = torch.zeros(G, dtype=torch.int32, device=dev)
+        # c1 reuse: the conv-A tiles the VALU pair forward stores for the pair backward
+        # (band-tile layout, csa_conv_pair_c1_size; CSA_PAIR_C1=0: the backward recomputes
+        # them).  Training programs of the VALU family only: serving never stores, the
+        # deterministic backward (cpv_bwd) and the MFMA-forward family keep the recompute.
+        self.pair_c1 = None
+        if (self.pair is not None and not fo and not self.det and os.environ.get("CSA_PAIR_C1", "1") == "1"
+                and self.lib.csa_conv_pair_valu_ok(_FK.ints(self.pair))):
+            n = _opt_call(self.lib, "csa_conv_pair_c1_size", _FK.ints(self.pair))
+            if n is not None and int(n) > 0:
+                self.pair_c1 = torch.zeros(int(n), **f32)
 
     def _plan_splits(self) -> None:
         """Split-K factor of each dense forward (> 1: its output is an atomic accumulator
@@ -1573,6 +1585,9 @@ class HipProgram:
             carrying = getattr(self, "carry", None) is not None and not getattr(self, "_predicting", False)
             if carrying:
                 self._rc(lib.csa_conv_pair_fwd_carry(*self._carry_args()), "conv_pair_fwd_carry")
+            c1 = None if getattr(self, "_predicting", False) else getattr(self, "pair_c1", None)
+            if c1 is not None:
+                _opt_call(lib, "csa_conv_pair_c1_fwd", K.ptr(c1), c1.numel())
             self._rc(lib.csa_conv_pair_fwd(
                 K.ints(self.pair), K.ptr(simg), K.ptr(srows), K.ptr(scur),
                 K.ptr(V[f"{ua.layer.name}.weight"]), K.ptr(V.get(f"{ua.layer.name}.bias")) if ua.layer.spec.bias else None,
@@ -1799,6 +1814,8 @@ class HipProgram:
         tab = getattr(nt, "bn_tab", None) if nt.has_bn else None
         if tab is not None and os.environ.get("CSA_PAIR_BN_TAB", "1") == "1":
             lib.csa_conv_pair_bn_tab(K.ptr(tab))
+        if getattr(self, "pair_c1", None) is not None:
+            _opt_call(lib, "csa_conv_pair_c1_bwd", K.ptr(self.pair_c1), self.pair_c1.numel())
         self._rc(lib.csa_conv_pair_bwd(
             K.ints(self.pair), K.ptr(simg), K.ptr(srows), K.ptr(scur),
             K.ptr(V[f"{ua.layer.name}.weight"]), K.ptr(V.get(f"{ua.layer.name}.bias")) if ua.layer.spec.bias else None,

@@ -58,6 +58,16 @@ def main() -> int:
     eng.step()
     torch.cuda.synchronize()
     eng.program.lib = rec.lib
+    # host state that a pair launch consumes (the BatchNorm tables, the stored c1 tiles):
+    # every replay of that launch sets it again first
+    last = {name: (fn, args) for name, fn, args in rec.calls}
+    consumed = {"csa_conv_pair_fwd": ("csa_conv_pair_c1_fwd",),
+                "csa_conv_pair_bwd": ("csa_conv_pair_bn_tab", "csa_conv_pair_c1_bwd")}
+
+    def arm(name):
+        for n in consumed.get(name, ()):
+            if n in last:
+                last[n][0](*last[n][1])
     if a.packed:
         rec.lib.csa_set_packed(1)       # replays outside the program's scope keep its shapes
     total = 0.0
@@ -149,6 +159,7 @@ def main() -> int:
                     for _ in range(3):
                         dbg.zero_()
                         eng.program.lib.csa_cp_debug(dbg.data_ptr())
+                        arm(name)
                         fn(*args)
                         torch.cuda.synchronize()
                         eng.program.lib.csa_cp_debug(None)
@@ -160,6 +171,7 @@ def main() -> int:
                 for _ in range(3):
                     dbg.zero_()
                     eng.program.lib.csa_cp_debug(dbg.data_ptr())
+                    arm(name)
                     fn(*args)
                     torch.cuda.synchronize()
                     eng.program.lib.csa_cp_debug(None)
@@ -209,6 +221,7 @@ def main() -> int:
             for _ in range(3):
                 life.zero_()
                 eng.program.lib.csa_cpv_life_debug(life.data_ptr())
+                arm(name)
                 fn(*args)
                 torch.cuda.synchronize()
                 eng.program.lib.csa_cpv_life_debug(None)
@@ -247,12 +260,14 @@ def main() -> int:
     if os.environ.get("MB_HF_ONLY"):        # e.g. MB_HF_ONLY=0: carry only the first deferred segment
         keep = {int(x) for x in os.environ["MB_HF_ONLY"].split(",")}
         defers = [d for i, d in enumerate(defers) if i in keep]
-    host_only = ("csa_dense_update_defer", "csa_dense_update_clear", "csa_dense_update_pending")
+    host_only = ("csa_dense_update_defer", "csa_dense_update_clear", "csa_dense_update_pending",
+                 "csa_conv_pair_c1_fwd", "csa_conv_pair_c1_bwd")
 
     def call(name, fn, args):
         if name == "csa_conv_pair_bwd":
             for dfn, dargs in defers:
                 dfn(*dargs)
+        arm(name)
         fn(*args)
 
     if os.environ.get("MB_HF"):
@@ -260,16 +275,17 @@ def main() -> int:
         # launches), and the pair backward carrying them
         lib = eng.program.lib
         pb = [(fn, args) for name, fn, args in rec.calls if name == "csa_conv_pair_bwd"][0]
-        tabs = [(fn, args) for name, fn, args in rec.calls if name == "csa_conv_pair_bn_tab"]
+        tabs = [name for name in consumed["csa_conv_pair_bwd"] if name in last]
         # MB_TAIL=1: the pair-backward tail too (its plan is consumed by each launch)
         tails = [(fn, args) for name, fn, args in rec.calls if name == "csa_conv_pair_tail_set"]
         tails = tails if os.environ.get("MB_TAIL") == "1" else []
-        if tabs or tails:                     # the BN-table pointer is consumed by each launch
+        if tabs or tails:                     # the BN-table / c1 pointers are consumed by each launch
             pb0 = pb
 
             def _pb(*args):
-                for tfn, targs in tails[-1:] + tabs[-1:]:
+                for tfn, targs in tails[-1:]:
                     tfn(*targs)
+                arm("csa_conv_pair_bwd")
                 pb0[0](*args)
             pb = (_pb, pb0[1])
 
