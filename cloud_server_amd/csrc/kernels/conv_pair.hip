@@ -31,6 +31,7 @@
 #include <vector>
 #include <cstdlib>
 #include <algorithm>
+#include <type_traits>
 
 namespace csa {
 
@@ -1350,15 +1351,21 @@ __global__ __launch_bounds__(CP_THREADS) void conv_pair_bwd_upd2_kernel(CPBwdArg
 //   conv A  one thread per c1 value of the band's tile (+ act A, zero outside the image);
 //           with CPVFwdArgs::c1 the tile also goes to global memory, in the LDS tile's
 //           order (band-tile layout, zero padding included), for the backward's prologue
-//   conv B  one thread per (unit pixel, output channel): the pool window's positions
-//           (+ bias, act B, max + argmax) with every weight read once per position
-//   stats   per-channel {sum, sum^2} of the band folded in fixed order, one row per band
-//           workgroup or an atomic fold into nslab rows
+//   conv B  one 16-lane row per (output channel pair, block of 16 units), lanes = units: the
+//           pool window's positions (+ bias, act B, max + argmax) from straight-line 64-bit
+//           c1 reads (two input channels) and 128-bit weight reads (two input x two output
+//           channels; the pool flag is a template parameter, so the window is compile-time)
+//   stats   per-channel {sum, sum^2}: a DPP row reduction of conv B's registers, lanes 0..3
+//           of the row store it (one row per workgroup) or add it atomically into nslab
+//           rows; bands wider than 16 units fold their rows' sums through LDS in fixed order
+// (__syncthreads() is s_waitcnt lgkmcnt(0) + s_barrier on gfx950: it does not wait for
+// outstanding global stores, so the y / argmax / c1 stores never hold a barrier.)
 // Family (cpv_ok): C0 <= 4, C1 <= 16, C2 <= 32, kernels <= 3x3, and the weights / input
 // tile fit one register batch of the workgroup.
 constexpr int CPV_T = 256;
 constexpr int CPV_MAXC1 = 16, CPV_MAXC2 = 32, CPV_MAXTAPS = 9;
 constexpr int CPV_UW = 8, CPV_UX = 2;                  // per-thread load batch (weights, x)
+constexpr int CPV_UB = CPV_UW / 2;                     // conv-B weights: float2 units per thread
 constexpr int CPV_MAXKA = 16;                          // conv-A taps x C0 held in registers
 
 struct CPVFwdArgs {
@@ -1368,11 +1375,33 @@ struct CPVFwdArgs {
   const float* wB; const float* bB; int actB; float alphaB;
   float* y; uint8_t* argmax; float* stat; int nslab;
   float* c1; int c1_stride;        // band tiles [B * nbands][c1_stride] kept for the backward, or null
+  // index divisors of the geometry (none depends on the band), built by the host
+  // (cpv_fwd_divs): an integer division in the kernel is ~30 VALU instructions on the chain
+  FastDiv dNb, dSlab;              // workgroup -> (image, band), -> slab row
+  FastDiv dC0, dXrow, dKAw;        // C0, TXW * C0 (x tile), conv-A kernel width
+  FastDiv dC1C2p;                  // conv-B weight float2 unit -> (tap, c1 * C2 / 2 + channel pair)
+  FastDiv dC1p, dT1W;              // conv-A thread -> (pixel slot, channel pair), pixel -> (ty, tx)
+  FastDiv dC2p, dOw;               // conv-B row task -> (unit block, channel pair), unit -> (py, px)
+  int nptA, nactA;                 // conv-A pixel slots CPV_T / (C1 / 2) and threads in use nptA * (C1 / 2)
 };
 
 __host__ __device__ inline int cpv_txw(const CPGeom& g) { return g.W2 + g.KBw - 1 + g.KAw - 1; }
 
-template <int KBH, int KBW, bool CARRY>
+// 16-lane row sum, every lane gets the total (the idiom of head_dgrad.h's row16_sum)
+__device__ __forceinline__ float cpv_row16_sum(float v) {
+  v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xb1, 0xf, 0xf, false));   // quad_perm 1,0,3,2
+  v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x4e, 0xf, 0xf, false));   // quad_perm 2,3,0,1
+  v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x141, 0xf, 0xf, false));  // row_half_mirror
+  v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x140, 0xf, 0xf, false));  // row_mirror
+  return v;
+}
+
+// Floats behind the c1 tile that conv B's window reads may touch: a pool window whose last
+// row / column lies outside conv B's output (odd H2 / W2 under a ceil-mode pool) reads one
+// tile row further; those positions never enter the max.
+__host__ __device__ inline int cpv_c1_slack(const CPGeom& g) { return g.pool ? (g.W2 + g.KBw) * g.C1 : 0; }
+
+template <int KBH, int KBW, bool POOL, bool CARRY>
 __global__ __launch_bounds__(CPV_T) void cpv_fwd_kernel(CPVFwdArgs a, CPZero z, CPOptCarry oc) {
   const CPGeom& g = a.g;
   // CARRY: the deferred dense update's workgroups follow the pair's (its own instantiation:
@@ -1382,31 +1411,41 @@ __global__ __launch_bounds__(CPV_T) void cpv_fwd_kernel(CPVFwdArgs a, CPZero z, 
     cp_opt_carry(oc, (int)blockIdx.x - npair, oc.blocks);
     return;
   }
-  __shared__ float s_w[CPV_UW * CPV_T];                 // [wA (KA x C1) | wB (KB x C2)]
+  // [wA (KA x C1) | pad to 4 | wB repacked: [c1 pair][c2 pair][tap] float4 {c1, c1+1} x {c2, c2+1}]
+  __shared__ __attribute__((aligned(16))) float s_w[CPV_UW * CPV_T];
   __shared__ int s_koffA[CPV_MAXKA];                    // x-tile offset of conv-A tap k
   __shared__ float s_b[CPV_MAXC1 + CPV_MAXC2];
   __shared__ float s_x[CPV_UX * CPV_T];
-  extern __shared__ __attribute__((aligned(16))) float smem[];   // c1 tile | unit outputs
-  const int b = blockIdx.x / g.nbands, band = blockIdx.x % g.nbands;
+  extern __shared__ __attribute__((aligned(16))) float smem[];   // c1 tile | slack | row partial sums
+  int b, band;
+  a.dNb.divmod((int)blockIdx.x, b, band);
   const int pr0 = band * g.PR, pr1 = min(g.PH, pr0 + g.PR);
-  const int r2a = g.pool ? 2 * pr0 : pr0, r2b = g.pool ? min(g.H2, 2 * pr1) : pr1;
+  const int r2a = POOL ? 2 * pr0 : pr0, r2b = POOL ? min(g.H2, 2 * pr1) : pr1;
   const CPBand t = cp_band(g, r2a, r2b);
   const int KA = g.KAh * g.KAw * g.C0, KB = g.KBh * g.KBw * g.C1;
-  const int nwA = KA * g.C1, nwA4 = (nwA + 3) & ~3, nw = nwA4 + KB * g.C2, nb = g.C1 + g.C2;
+  const int nwA = KA * g.C1, nwA4 = (nwA + 3) & ~3, nb = g.C1 + g.C2;
   const int nX = t.TXH * t.TXW * g.C0;
   const int tid = threadIdx.x;
   CP_STAMP(0);
   if (g_cpv_life && tid == 0) g_cpv_life[2 * blockIdx.x] = (long long)__builtin_amdgcn_s_memrealtime();
   // ---- one batch of loads: weights + biases first, then the image rows (the staged
   // image is at a fixed address; otherwise its row index chain runs under the weights).
-  // LDS weights: [wA | pad to 4 | wB] (wB read as float2 / float4 rows)
-  float wv[CPV_UW];
+  // LDS weights: [wA | pad to 4 | wB repacked] — conv B reads the four weights of (two input
+  // channels x two output channels) of a tap as one float4; the repacked store address is
+  // computed while the loads are in flight
+  constexpr int NT = KBH * KBW;
+  const int ncp = g.C2 >> 1;
+  // wA: one value per thread.  wB: float2 units (c2, c2 + 1) of the [tap][c1][C2] tensor,
+  // CPV_UB per thread (batches wholly past the weights: not issued)
+  const int nwB2 = KB * ncp;
+  float wa = 0.f;
+  if (tid < nwA) wa = a.wA[tid];
+  float2 wv[CPV_UB];
 #pragma unroll
-  for (int u = 0; u < CPV_UW; ++u) {                     // (batches wholly past the weights:
-    const int e = u * CPV_T + tid;                          //  not issued)
-    const float* p = e < nwA ? a.wA + e : (e >= nwA4 && e < nw ? a.wB + (e - nwA4) : a.wA);
-    wv[u] = 0.f;
-    if (u * CPV_T < nw) wv[u] = *p;
+  for (int u = 0; u < CPV_UB; ++u) {
+    const int e = u * CPV_T + tid;
+    wv[u] = make_float2(0.f, 0.f);
+    if (u * CPV_T < nwB2) wv[u] = reinterpret_cast<const float2*>(a.wB)[e < nwB2 ? e : 0];
   }
   float bv = 0.f;
   if (tid < nb) bv = tid < g.C1 ? (a.bA ? a.bA[tid] : 0.f) : (a.bB ? a.bB[tid - g.C1] : 0.f);
@@ -1417,69 +1456,110 @@ __global__ __launch_bounds__(CPV_T) void cpv_fwd_kernel(CPVFwdArgs a, CPZero z, 
 #pragma unroll
   for (int u = 0; u < CPV_UX; ++u) {
     const int e = u * CPV_T + tid;
-    const int c = e % g.C0, rem = e / g.C0, xx = rem % t.TXW, r = rem / t.TXW;
-    const int yy = y0 + r, xg = x0 + xx;
-    xok[u] = e < nX && yy >= 0 && yy < g.H && xg >= 0 && xg < g.W;
+    xok[u] = false;
     xv[u] = 0;
-    if (u * CPV_T < nX) xv[u] = src[xok[u] ? ((long)yy * g.W + xg) * g.C0 + c : 0];
+    if (u * CPV_T < nX) {                                    // (uniform)
+      int c, rem, xx, r;
+      a.dXrow.divmod(e, r, rem);
+      a.dC0.divmod(rem, xx, c);
+      const int yy = y0 + r, xg = x0 + xx;
+      xok[u] = e < nX && yy >= 0 && yy < g.H && xg >= 0 && xg < g.W;
+      xv[u] = src[xok[u] ? ((long)yy * g.W + xg) * g.C0 + c : 0];
+    }
   }
+  CP_STAMP(7);                                            // loads issued (1: landed and staged)
+  int wdst[CPV_UB];
 #pragma unroll
-  for (int u = 0; u < CPV_UW; ++u) pin(wv[u]);
-#pragma unroll
-  for (int u = 0; u < CPV_UW; ++u) {
-    const int e = u * CPV_T + tid;
-    if (e < nw) s_w[e] = wv[u];
+  for (int u = 0; u < CPV_UB; ++u) {
+    wdst[u] = 0;
+    if (u * CPV_T < nwB2) {                                  // unit (tap k, c1, channel pair cp)
+      int k, rem, c1, cp;
+      a.dC1C2p.divmod(u * CPV_T + tid, k, rem);
+      a.dC2p.divmod(rem, c1, cp);
+      wdst[u] = nwA4 + (((((c1 >> 1) * ncp + cp) * NT + k) << 2) | ((c1 & 1) << 1));
+    }
   }
+  int koffA = 0;
+  if (tid < KA) {
+    int c0, ij, i, j;
+    a.dC0.divmod(tid, ij, c0);
+    a.dKAw.divmod(ij, i, j);
+    koffA = (i * t.TXW + j) * g.C0 + c0;
+  }
+  pin(wa);
+#pragma unroll
+  for (int u = 0; u < CPV_UB; ++u) { pin(wv[u].x); pin(wv[u].y); }
+  if (tid < nwA) s_w[tid] = wa;
+#pragma unroll
+  for (int u = 0; u < CPV_UB; ++u)
+    if (u * CPV_T + tid < nwB2) *reinterpret_cast<float2*>(s_w + wdst[u]) = wv[u];
   if (tid < nb) s_b[tid] = bv;
 #pragma unroll
   for (int u = 0; u < CPV_UX; ++u) {
     const int e = u * CPV_T + tid;
     if (e < nX) s_x[e] = xok[u] ? (float)xv[u] * (1.0f / 255.0f) : 0.f;
   }
-  if (tid < KA) {
-    const int c0 = tid % g.C0, ij = tid / g.C0, i = ij / g.KAw, j = ij - i * g.KAw;
-    s_koffA[tid] = (i * t.TXW + j) * g.C0 + c0;
-  }
+  if (tid < KA) s_koffA[tid] = koffA;
   __syncthreads();
   CP_STAMP(1);
   // ---- conv A: the c1 tile [T1H][T1W][C1] (zero outside [0, H1) x [0, W1)): one thread
-  // per (tile pixel, channel pair) — all 256 threads busy (one thread per pixel left 2/3 of
-  // them idle behind a C1/2-long chain) — tap offsets held in registers
+  // per (tile pixel, channel pair) (one thread per pixel left 2/3 of them idle behind a
+  // C1/2-long chain).  Thread = (pixel slot, channel pair) and the item stride is a multiple
+  // of C1/2, so a thread keeps its channel pair over its items: tap offsets, tap weights and
+  // biases are read once into registers; items stay consecutive over consecutive threads
   float* s_c1 = smem;
   const int npx1 = t.T1H * t.T1W;
   {
-    int koff[CPV_MAXKA];
-#pragma unroll
-    for (int k = 0; k < CPV_MAXKA; ++k) koff[k] = k < KA ? s_koffA[k] : 0;
     const int nc1p = g.C1 >> 1, nit = npx1 * nc1p;
+    int slot, cp;
+    a.dC1p.divmod(tid, slot, cp);
+    const int c1 = 2 * cp;
+    const float bA0 = s_b[c1], bA1 = s_b[c1 + 1];
     // the tile also goes out for the backward (a.c1: band-tile layout, the LDS tile's own
     // order with its zero padding, so the backward's load is one contiguous copy); the
     // stores drain under conv B.  Past the tile, up to the stride: zeros (the backward's
     // last band is one row taller when H2 is odd — a row only zero gradients meet)
     float* gc1 = a.c1 ? a.c1 + (long)blockIdx.x * a.c1_stride : nullptr;
     const int nst = gc1 ? max(nit, a.c1_stride >> 1) : nit;     // (host: stride >= every band's tile)
-    for (int it = tid; it < nst; it += CPV_T) {
-      float2 v = make_float2(0.f, 0.f);
-      if (it < nit) {
-        const int cp = it % nc1p, pix = it / nc1p, c1 = 2 * cp;
-        const int tx = pix % t.T1W, ty = pix / t.T1W;
-        const int yy = t.c1y0 + ty, xx = tx - g.PLB;
-        const bool in = yy >= 0 && yy < g.H1 && xx >= 0 && xx < g.W1;
-        const float* xb = s_x + (ty * t.TXW + tx) * g.C0;
-        float a0 = s_b[c1], a1 = s_b[c1 + 1];
+    // register capacity NK >= KA taps chosen by a uniform branch (the sample's four taps
+    // preload 4 offsets + 4 weight pairs, not 16 + 16)
+    auto conv_a = [&](auto nk) {
+      constexpr int NK = decltype(nk)::value;
+      int koff[NK];
+      float wk0[NK], wk1[NK];
 #pragma unroll
-        for (int k = 0; k < CPV_MAXKA; ++k) {
-          if (k >= KA) break;                                 // uniform
-          const float xv = xb[koff[k]];
-          const float2 w = *reinterpret_cast<const float2*>(s_w + k * g.C1 + c1);
-          a0 = fmaf(xv, w.x, a0);
-          a1 = fmaf(xv, w.y, a1);
-        }
-        if (in) v = make_float2(act_fwd(a0, a.actA, a.alphaA), act_fwd(a1, a.actA, a.alphaA));
-        *reinterpret_cast<float2*>(s_c1 + pix * g.C1 + c1) = v;
+      for (int k = 0; k < NK; ++k) {
+        koff[k] = k < KA ? s_koffA[k] : 0;
+        const float2 w = *reinterpret_cast<const float2*>(s_w + (k < KA ? k : 0) * g.C1 + c1);
+        wk0[k] = w.x;
+        wk1[k] = w.y;
       }
-      if (gc1) out_store2(gc1 + 2 * it, v.x, v.y);
-    }
+      // item it = pix * nc1p + cp; thread (slot, cp) takes pixels slot, slot + nptA, ...
+      for (int it = tid, pix = slot; it < nst && tid < a.nactA; it += a.nactA, pix += a.nptA) {
+        float2 v = make_float2(0.f, 0.f);
+        if (it < nit) {
+          int ty, tx;
+          a.dT1W.divmod(pix, ty, tx);
+          const int yy = t.c1y0 + ty, xx = tx - g.PLB;
+          const bool in = yy >= 0 && yy < g.H1 && xx >= 0 && xx < g.W1;
+          const float* xb = s_x + (ty * t.TXW + tx) * g.C0;
+          float a0 = bA0, a1 = bA1;
+#pragma unroll
+          for (int k = 0; k < NK; ++k) {
+            if (k >= KA) break;                                 // uniform
+            const float xv = xb[koff[k]];
+            a0 = fmaf(xv, wk0[k], a0);
+            a1 = fmaf(xv, wk1[k], a1);
+          }
+          if (in) v = make_float2(act_fwd(a0, a.actA, a.alphaA), act_fwd(a1, a.actA, a.alphaA));
+          *reinterpret_cast<float2*>(s_c1 + 2 * it) = v;        // = s_c1 + pix * C1 + c1
+        }
+        if (gc1) out_store2(gc1 + 2 * it, v.x, v.y);
+      }
+    };
+    if (KA <= 4) conv_a(std::integral_constant<int, 4>{});
+    else if (KA <= 9) conv_a(std::integral_constant<int, 9>{});
+    else conv_a(std::integral_constant<int, CPV_MAXKA>{});
   }
   __syncthreads();
   CP_STAMP(2);
@@ -1488,88 +1568,119 @@ __global__ __launch_bounds__(CPV_T) void cpv_fwd_kernel(CPVFwdArgs a, CPZero z, 
   // are loaded once and feed every (position, tap) FMA: 4 x taps x 2 FMAs per ~WR WC + taps loads
   const int ow = g.pool ? g.PW : g.W2;
   const int nunit = (g.pool ? (pr1 - pr0) : (r2b - r2a)) * ow;
-  const int nout = nunit * g.C2;
-  float* s_out = s_c1 + ((npx1 * g.C1 + 3) & ~3);          // [nunit][C2] outputs for the stats
-  const float* wB = s_w + nwA4;
-  constexpr int WR = KBH + 1, WC = KBW + 1;                // pool window footprint in c1
-  const int ncp = g.C2 >> 1, npos = g.pool ? 4 : 1;
-  for (int o = tid; o < nunit * ncp; o += CPV_T) {
-    const int cp = o % ncp, u = o / ncp, py = u / ow, px = u - py * ow, c2 = 2 * cp;
-    const int y2b = g.pool ? 2 * (pr0 + py) : r2a + py, x2b = g.pool ? 2 * px : px;
-    float acc[4][2];
+  // row partial sums [row task][4] of the bands wider than one row
+  float* s_sp = s_c1 + ((npx1 * g.C1 + cpv_c1_slack(g) + 3) & ~3);
+  const float4* wB4 = reinterpret_cast<const float4*>(s_w + nwA4);
+  constexpr int WR = POOL ? KBH + 1 : KBH, WC = POOL ? KBW + 1 : KBW;   // window footprint in c1
+  constexpr int NPOS = POOL ? 4 : 1;
+  const int nur = (nunit + 15) >> 4, ntask = nur * ncp;
+  const int lane = tid & 15, row = tid >> 4, wrow = (tid >> 6) << 2;
+  // nslab >= workgroups: one exclusive row per workgroup, plain stores (deterministic mode)
+  int slab = (int)blockIdx.x;
+  if (a.nslab < npair) slab -= a.dSlab.div(slab) * a.nslab;
+  float* srow = a.stat ? a.stat + (size_t)slab * 2 * g.C2 : nullptr;
+  // whole waves enter (wave-uniform bound): the row reductions below read every lane
+  for (int r0 = 0; r0 + wrow < ntask; r0 += CPV_T / 16) {
+    const bool rowok = r0 + row < ntask;
+    const int rt = rowok ? r0 + row : ntask - 1;
+    int ur, cp;
+    a.dC2p.divmod(rt, ur, cp);
+    const int c2 = 2 * cp;
+    const bool ok = rowok && ur * 16 + lane < nunit;
+    const int u = min(ur * 16 + lane, nunit - 1);            // idle lanes: a valid unit, nothing stored
+    int py, px;
+    a.dOw.divmod(u, py, px);
+    const int y2b = POOL ? 2 * (pr0 + py) : r2a + py, x2b = POOL ? 2 * px : px;
+    float acc[NPOS][2];
     const float b0 = s_b[g.C1 + c2], b1 = s_b[g.C1 + c2 + 1];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) { acc[q][0] = b0; acc[q][1] = b1; }
+    for (int q = 0; q < NPOS; ++q) { acc[q][0] = b0; acc[q][1] = b1; }
     const float* cb = s_c1 + ((y2b - r2a) * t.T1W + x2b) * g.C1;
-    const bool wide = g.pool != 0;                           // window rows/cols beyond KBH x KBW
+    const float4* wp = wB4 + cp * NT;
+    const int nc1p = g.C1 >> 1;
 #pragma unroll 2
-    for (int c1 = 0; c1 < g.C1; ++c1) {
-      float cv[WR][WC];
+    for (int p = 0; p < nc1p; ++p) {                         // two input channels per step
+      float2 cv[WR][WC];
 #pragma unroll
       for (int r = 0; r < WR; ++r)
 #pragma unroll
         for (int c = 0; c < WC; ++c)
-          cv[r][c] = (wide || (r < KBH && c < KBW)) ? cb[(r * t.T1W + c) * g.C1 + c1] : 0.f;
-      float2 wv[KBH * KBW];
+          cv[r][c] = *reinterpret_cast<const float2*>(cb + (r * t.T1W + c) * g.C1 + 2 * p);
+      float4 wv[NT];
 #pragma unroll
-      for (int k = 0; k < KBH * KBW; ++k)
-        wv[k] = *reinterpret_cast<const float2*>(wB + (k * g.C1 + c1) * g.C2 + c2);
+      for (int k = 0; k < NT; ++k) wv[k] = wp[p * ncp * NT + k];
+      // each accumulator: channel 2p's taps in order, then channel 2p + 1's (the order of
+      // one channel per step)
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
+      for (int q = 0; q < NPOS; ++q) {
         const int dy = q >> 1, dx = q & 1;
 #pragma unroll
         for (int i = 0; i < KBH; ++i)
 #pragma unroll
           for (int j = 0; j < KBW; ++j) {
-            acc[q][0] = fmaf(cv[dy + i][dx + j], wv[i * KBW + j].x, acc[q][0]);
-            acc[q][1] = fmaf(cv[dy + i][dx + j], wv[i * KBW + j].y, acc[q][1]);
+            acc[q][0] = fmaf(cv[dy + i][dx + j].x, wv[i * KBW + j].x, acc[q][0]);
+            acc[q][1] = fmaf(cv[dy + i][dx + j].x, wv[i * KBW + j].y, acc[q][1]);
+          }
+      }
+#pragma unroll
+      for (int q = 0; q < NPOS; ++q) {
+        const int dy = q >> 1, dx = q & 1;
+#pragma unroll
+        for (int i = 0; i < KBH; ++i)
+#pragma unroll
+          for (int j = 0; j < KBW; ++j) {
+            acc[q][0] = fmaf(cv[dy + i][dx + j].y, wv[i * KBW + j].z, acc[q][0]);
+            acc[q][1] = fmaf(cv[dy + i][dx + j].y, wv[i * KBW + j].w, acc[q][1]);
           }
       }
     }
     float best0 = -INFINITY, best1 = -INFINITY;
     int am0 = 0, am1 = 0;
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      if (q >= npos) break;
+    for (int q = 0; q < NPOS; ++q) {
       const int y2 = y2b + (q >> 1), x2 = x2b + (q & 1);
       if (y2 >= g.H2 || x2 >= g.W2) continue;
       const float v0 = act_fwd(acc[q][0], a.actB, a.alphaB), v1 = act_fwd(acc[q][1], a.actB, a.alphaB);
       if (v0 > best0) { best0 = v0; am0 = q; }
       if (v1 > best1) { best1 = v1; am1 = q; }
     }
-    const int oo = u * g.C2 + c2;
-    const long off = g.pool ? (((long)b * g.PH + pr0) * g.PW) * g.C2 + oo
+    if (ok) {
+      const int oo = u * g.C2 + c2;
+      const long off = POOL ? (((long)b * g.PH + pr0) * g.PW) * g.C2 + oo
                             : (((long)b * g.H2 + r2a) * g.W2) * g.C2 + oo;
-    out_store2(a.y + off, best0, best1);
-    if (g.pool && a.argmax) {
-      a.argmax[off] = (uint8_t)am0;
-      a.argmax[off + 1] = (uint8_t)am1;
-    }
-    *reinterpret_cast<float2*>(s_out + oo) = make_float2(best0, best1);
-  }
-  (void)nout;
-  CP_STAMP(3);
-  if (a.stat) {                                           // per-channel sums, fixed order
-    // (column, unit slice) per thread, slices combined in order
-    __shared__ float s_sp[CPV_T];
-    __syncthreads();
-    const int cols = 2 * g.C2, nsl = max(1, CPV_T / cols), per = (nunit + nsl - 1) / nsl;
-    if (tid < cols * nsl) {
-      const int col = tid % cols, sl = tid / cols, c = col % g.C2, sq = col / g.C2;
-      float acc = 0.f;
-      for (int u = sl * per; u < min(nunit, (sl + 1) * per); ++u) {
-        const float v = s_out[u * g.C2 + c];
-        acc += sq ? v * v : v;
+      out_store2(a.y + off, best0, best1);
+      if (POOL && a.argmax) {
+        a.argmax[off] = (uint8_t)am0;
+        a.argmax[off + 1] = (uint8_t)am1;
       }
-      s_sp[tid] = acc;
     }
+    if (a.stat) {
+      // per-channel {sum, sum^2} of the row's units from the registers (fixed order): lanes
+      // 0..3 of the row write {s0, s1, q0, q1} — to the slab row when the band's units fill
+      // one row, else to LDS for the fold below
+      const float v0 = ok ? best0 : 0.f, v1 = ok ? best1 : 0.f;
+      const float s0 = cpv_row16_sum(v0), s1 = cpv_row16_sum(v1);
+      const float q0 = cpv_row16_sum(v0 * v0), q1 = cpv_row16_sum(v1 * v1);
+      if (rowok && lane < 4) {
+        const float v = lane == 0 ? s0 : lane == 1 ? s1 : lane == 2 ? q0 : q1;
+        if (nur > 1) s_sp[rt * 4 + lane] = v;
+        else {
+          float* dst = srow + (lane >> 1) * g.C2 + c2 + (lane & 1);
+          if (a.nslab >= npair) *dst = v;
+          else atomicAdd(dst, v);
+        }
+      }
+    }
+  }
+  CP_STAMP(3);
+  if (a.stat && nur > 1) {                                // unit blocks of a channel folded in order
     __syncthreads();
-    if (tid < cols) {
+    if (tid < 2 * g.C2) {
+      const int sq = tid >= g.C2, c = tid - sq * g.C2, j = sq * 2 + (c & 1);
       float acc = 0.f;
-      for (int sl = 0; sl < nsl; ++sl) acc += s_sp[sl * cols + tid];
-      float* row = a.stat + (size_t)(blockIdx.x % a.nslab) * 2 * g.C2;
-      if (a.nslab >= npair) row[tid] = acc;                    // one row per workgroup
-      else atomicAdd(&row[tid], acc);
+      for (int ur = 0; ur < nur; ++ur) acc += s_sp[(ur * ncp + (c >> 1)) * 4 + j];
+      if (a.nslab >= npair) srow[tid] = acc;
+      else atomicAdd(&srow[tid], acc);
     }
   }
   cp_zero_early(z, npair);            // (at the end: stores in front would delay the loads)
@@ -1978,7 +2089,37 @@ static size_t cpv_fwd_lds(const CPGeom& g) {
   const int rows = g.pool ? 2 * g.PR : g.PR;
   const int T1H = rows + g.KBh - 1, T1W = g.W2 + g.KBw - 1;
   const int units = (g.pool ? g.PR * g.PW : g.PR * g.W2);
-  return (size_t)(((T1H * T1W * g.C1 + 3) & ~3) + units * g.C2) * sizeof(float);
+  // c1 tile | slack for the pool windows | row partial sums [unit block][C2 / 2][4]
+  return (size_t)(((T1H * T1W * g.C1 + cpv_c1_slack(g) + 3) & ~3) + ((units + 15) / 16) * 2 * g.C2) * sizeof(float);
+}
+
+// The kernel's index divisors (band-independent).
+static void cpv_fwd_divs(CPVFwdArgs& v) {
+  const CPGeom& g = v.g;
+  v.dNb = FastDiv(g.nbands);
+  v.dSlab = FastDiv(v.nslab);
+  v.dC0 = FastDiv(g.C0);
+  v.dXrow = FastDiv(cpv_txw(g) * g.C0);
+  v.dKAw = FastDiv(g.KAw);
+  v.dC1C2p = FastDiv(g.C1 * (g.C2 / 2));
+  v.dC1p = FastDiv(g.C1 / 2);
+  v.dT1W = FastDiv(g.W2 + g.KBw - 1);
+  v.dC2p = FastDiv(g.C2 / 2);
+  v.dOw = FastDiv(g.pool ? g.PW : g.W2);
+  v.nptA = CPV_T / (g.C1 / 2);
+  v.nactA = v.nptA * (g.C1 / 2);
+}
+
+template <int KBH, int KBW>
+static void cpv_fwd_launch(const CPVFwdArgs& v, const CPZero& z, const CPOptCarry& oc, unsigned grid, hipStream_t st) {
+  const size_t lds = cpv_fwd_lds(v.g);
+  if (v.g.pool) {
+    if (oc.blocks) hipLaunchKernelGGL((cpv_fwd_kernel<KBH, KBW, true, true>), dim3(grid), dim3(CPV_T), lds, st, v, z, oc);
+    else hipLaunchKernelGGL((cpv_fwd_kernel<KBH, KBW, true, false>), dim3(grid), dim3(CPV_T), lds, st, v, z, oc);
+  } else {
+    if (oc.blocks) hipLaunchKernelGGL((cpv_fwd_kernel<KBH, KBW, false, true>), dim3(grid), dim3(CPV_T), lds, st, v, z, oc);
+    else hipLaunchKernelGGL((cpv_fwd_kernel<KBH, KBW, false, false>), dim3(grid), dim3(CPV_T), lds, st, v, z, oc);
+  }
 }
 
 static bool cp_geom(const int* v, CPGeom& g) {
@@ -2216,19 +2357,16 @@ CSA_API int csa_conv_pair_fwd(const int* geom, const uint8_t* img, const int64_t
   if (cpv_ok(a.g)) {
     CPVFwdArgs v{a.g, img, idx, cursor, wA, bA, actA, alphaA, wB, bB, actB, alphaB, y, argmax, stat, a.nslab,
                  nullptr, 0};
+    if ((uintptr_t)wB & 7) return -2;                  // conv-B weights are loaded as float2
     if (c1) {
       const int stride = cp_c1_stride(a.g);
       if (!stride || ((uintptr_t)c1 & 15) || c1n < (long)stride * a.g.B * a.g.nbands) return -8;
       v.c1 = c1; v.c1_stride = stride;
     }
     const unsigned grid = (unsigned)(a.g.B * a.g.nbands + oc.blocks);
-    if (oc.blocks) {
-      if (a.g.KBh == 2) hipLaunchKernelGGL((cpv_fwd_kernel<2, 2, true>), dim3(grid), dim3(CPV_T), cpv_fwd_lds(a.g), st, v, z, oc);
-      else hipLaunchKernelGGL((cpv_fwd_kernel<3, 3, true>), dim3(grid), dim3(CPV_T), cpv_fwd_lds(a.g), st, v, z, oc);
-    } else {
-      if (a.g.KBh == 2) hipLaunchKernelGGL((cpv_fwd_kernel<2, 2, false>), dim3(grid), dim3(CPV_T), cpv_fwd_lds(a.g), st, v, z, oc);
-      else hipLaunchKernelGGL((cpv_fwd_kernel<3, 3, false>), dim3(grid), dim3(CPV_T), cpv_fwd_lds(a.g), st, v, z, oc);
-    }
+    cpv_fwd_divs(v);
+    if (a.g.KBh == 2) cpv_fwd_launch<2, 2>(v, z, oc, grid, st);
+    else cpv_fwd_launch<3, 3>(v, z, oc, grid, st);
     return (int)hipGetLastError();
   }
   if (oc.blocks) return -7;                        // only the VALU forward carries the update

@@ -164,7 +164,11 @@ def main() -> int:
                         torch.cuda.synchronize()
                         eng.program.lib.csa_cp_debug(None)
                     t = dbg.tolist()
-                    print(f"{i:2d} {name} block {blk}: stage {t[1]-t[0]} convA {t[2]-t[1]} convB+pool {t[3]-t[2]} "
+                    # (stamp 7, VALU forward: every load issued — index arithmetic before it,
+                    # memory latency + LDS staging after it; conv B's stamp includes the row
+                    # statistics, "stats" the LDS fold of wide bands and the zero list)
+                    split = f" (issue {t[7]-t[0]} land {t[1]-t[7]})" if t[7] else ""
+                    print(f"{i:2d} {name} block {blk}: stage {t[1]-t[0]}{split} convA {t[2]-t[1]} convB+pool {t[3]-t[2]} "
                           f"stats {t[4]-t[3]} (s_memtime ticks)")
                 eng.program.lib.csa_cp_debug_block(0)
             elif name.startswith("csa_conv_pair_"):
