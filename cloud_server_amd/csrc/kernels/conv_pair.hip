@@ -17,8 +17,10 @@
 //            loaded with the prologue's loads from the tile the VALU forward stored (or
 //            recomputed from the input rows: the MFMA-forward family, CSA_PAIR_C1=0 —
 //            a K = 4 GEMM phase of ~2 us in a latency chain, profiles/r7_notes.md),
-//            conv B's weight gradient, conv B's input gradient dc1 (through act A),
-//            conv A's weight gradient — all from LDS; the weight gradients leave the
+//            conv B's weight gradient, conv B's input gradient dc1 (through act A) — the
+//            tiles of these two GEMMs split over the waves by a host plan (round 9) —,
+//            conv A's weight gradient, the bias gradients as a spare M row of those GEMMs
+//            fed 1.0 (none without a bias) — all from LDS; the weight gradients leave the
 //            launch as one atomic add per (workgroup, weight) into S stripes that the
 //            optimizer folds.  No dc2 / dc1 tensor is ever written.
 //
@@ -333,34 +335,50 @@ __device__ __forceinline__ void cp_stage_fwd_inputs(const CPGeom& g, const CPBan
 // 16x16x4 map: A lane l = A[l&15][l>>4], B lane l = B[l>>4][l&15], D[4*(l>>4)+r][l&15].
 typedef float cp_f32x4 __attribute__((ext_vector_type(4)));
 
+//
+// One (tm, tn) tile is a UNIT (cp_gemm_unit): its FMA order is fixed, so which wave runs a
+// unit never changes a result.  ONES: the lane whose A row is `ones` feeds 1.0 instead of
+// its gather, which makes D's row `ones` the column sums of B over k (a padding row of M
+// put to use: the pair backward's bias gradients; ones < 0: no such row).
+template <bool ONES, class FA, class FB, class FE>
+__device__ __forceinline__ void cp_gemm_unit(const float* s, int tm, int tn, int ksteps, const int* aoff,
+                                             const int* boff, FA abase, FB bbase, FE epi, int ones = -1) {
+  const int lane = threadIdx.x & 63, i16 = lane & 15, q = lane >> 4;
+  const float* pa = s + abase(tm * 16 + i16);
+  const float* pb = s + bbase(tn * 16 + i16);
+  const bool one = ONES && tm * 16 + i16 == ones;
+  cp_f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+  int ks = 0;
+  for (; ks + 4 <= ksteps; ks += 4) {
+    float av[4], bv[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int k = 4 * (ks + u) + q;
+      av[u] = pa[aoff[k]];
+      if (ONES) av[u] = one ? 1.0f : av[u];
+      bv[u] = pb[boff[k]];
+    }
+    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[0], bv[0], acc0, 0, 0, 0);
+    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[1], bv[1], acc1, 0, 0, 0);
+    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[2], bv[2], acc0, 0, 0, 0);
+    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[3], bv[3], acc1, 0, 0, 0);
+  }
+  for (; ks < ksteps; ++ks) {
+    const int k = 4 * ks + q;
+    float av = pa[aoff[k]];
+    if (ONES) av = one ? 1.0f : av;
+    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av, pb[boff[k]], acc0, 0, 0, 0);
+  }
+  epi(tm, tn, acc0 + acc1, 0);
+}
+
 template <class FA, class FB, class FE>
 __device__ __forceinline__ void cp_gemm(const float* s, int mt, int nt, int ksteps, const int* aoff, const int* boff,
                                         FA abase, FB bbase, FE epi) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i16 = lane & 15, q = lane >> 4;
+  const int wave = threadIdx.x >> 6;
   for (int pr = wave; pr < mt * nt; pr += CP_THREADS / 64) {
     const int tm = pr / nt, tn = pr - tm * nt;
-    const float* pa = s + abase(tm * 16 + i16);
-    const float* pb = s + bbase(tn * 16 + i16);
-    cp_f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-    int ks = 0;
-    for (; ks + 4 <= ksteps; ks += 4) {
-      float av[4], bv[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int k = 4 * (ks + u) + q;
-        av[u] = pa[aoff[k]];
-        bv[u] = pb[boff[k]];
-      }
-      acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[0], bv[0], acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[1], bv[1], acc1, 0, 0, 0);
-      acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[2], bv[2], acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[3], bv[3], acc1, 0, 0, 0);
-    }
-    for (; ks < ksteps; ++ks) {
-      const int k = 4 * ks + q;
-      acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(pa[aoff[k]], pb[boff[k]], acc0, 0, 0, 0);
-    }
-    epi(tm, tn, acc0 + acc1, 0);
+    cp_gemm_unit<false>(s, tm, tn, ksteps, aoff, boff, abase, bbase, epi);
   }
 }
 
@@ -544,6 +562,11 @@ struct CPBwdArgs {
   unsigned* img_tk;                 // tail: +1 per workgroup once its image tile is in LDS (or null)
   const float* bn_tab;              // [mean | rstd | a | b][C2] the step's bn_act_apply wrote, or null
   const float* c1; int c1_stride;   // band tiles [B * nbands][c1_stride] the VALU forward stored (g.c1r)
+  // host-built divisors (cp_bwd_divs): no integer division is expanded in the workgroup
+  FastDiv dNb, dStripes;            // workgroup -> (image, band), -> stripe
+  FastDiv dC2x2, dC2, dC1;          // thread -> slab (row, column); weight -> (tap, channel)
+  FastDiv dOw, dW1, dBias;          // unit row width, c1 row width, C2 + C1 (bias loop)
+  int sper, bper;                   // 256 / (2 C2), 256 / (C2 + C1)
 };
 
 // LDS carve of the backward (float offsets), shared by the kernel and the host size check.
@@ -593,11 +616,43 @@ __host__ __device__ inline CPBwdLayout cp_bwd_layout(const CPGeom& g, int band, 
   const int rsz = rmain + (rA_in_dc2 ? 0 : 4 * 16 * 16);
   L.red = o; o += ((rsz > 8 * CP_MAXC2 ? rsz : 8 * CP_MAXC2) + 3) & ~3;
   L.rA = rA_in_dc2 ? L.dc2 : L.red + rmain;
+  // int tables; the 16 ints after the n16b tap offsets hold the dwB + dc1 unit plan (CP_PLAN_INTS)
   L.offs = o; o += (c1r ? 1 : 2) * L.kpadA + L.kp2 * 2 + L.kpadD * 2 + L.kp1 * 2 + L.n16b + 16;
   L.end = o;
   (void)L.wA;
   return L;
 }
+
+// Unit plan of the backward's two big in-LDS GEMMs (round 9).  dwB ([n16b / 16] x [c16 / 16]
+// tiles of kp2 / 4 k-steps) and dc1 ([npix1 / 16] tiles of kpadD / 4 k-steps) share no
+// barrier and neither reads what the other writes, so their tiles are ONE list of units for
+// the four waves.  Dealing each GEMM round-robin (pr = wave, wave + 4, ..) gives the sample's
+// waves 48, 48, 34, 34 k-steps; the best split is 40, 40, 42, 42.  The plan is 16 ints at the
+// end of the tap table (the table's spare tail), four per wave:
+//   {first dwB unit | count << 16,  that unit's tm | tn << 16,  first dc1 unit | count << 16,
+//    unit stride}
+// A wave runs its dwB units, then its dc1 units.  The round-robin dealing is the same
+// record with stride 4 (cp_bwd_plan_dealt: what a workgroup without a host plan uses); a
+// host plan (cp_bwd_plan) gives every wave a contiguous range, stride 1.  Units of one GEMM
+// are equal, so an optimal split never needs more than ranges.
+constexpr int CP_PLAN_INTS = 16;
+struct CPUnits { int nB, ntB, kB, nD, kD; };
+__host__ __device__ inline CPUnits cp_bwd_units(const CPBwdLayout& L) {
+  return CPUnits{(L.n16b >> 4) * (L.c16 >> 4), L.c16 >> 4, L.kp2 >> 2, (L.npix1 + 15) >> 4, L.kpadD >> 2};
+}
+__host__ __device__ inline void cp_plan_wave(int* w4, int ntB, int b0, int nb, int d0, int nd, int stride) {
+  int tm = 0, tn = b0;
+  while (tn >= ntB) { tn -= ntB; ++tm; }
+  w4[0] = b0 | nb << 16; w4[1] = tm | tn << 16; w4[2] = d0 | nd << 16; w4[3] = stride;
+}
+__device__ __forceinline__ void cp_bwd_plan_dealt(const CPBwdLayout& L, int* s_plan) {
+  const int w = threadIdx.x;
+  if (w >= 4) return;
+  const CPUnits u = cp_bwd_units(L);
+  cp_plan_wave(s_plan + 4 * w, u.ntB, w, w < u.nB ? (u.nB - w + 3) >> 2 : 0, w, w < u.nD ? (u.nD - w + 3) >> 2 : 0, 4);
+}
+// a host plan per band class (0: every band but the last, 1: the last band), for the table kernel
+struct CPPlans { int on[2]; int w[2][CP_PLAN_INTS]; };
 
 // The backward's per-band index tables (they depend on the band only): into the int region
 // at s_offA (layout: see cp_bwd_body).  Computed once per geometry into global memory by
@@ -651,6 +706,7 @@ __device__ __forceinline__ void cp_bwd_tables(const CPGeom& g, const CPBand& t, 
       }
       s_tapB[k] = o;
     }
+    cp_bwd_plan_dealt(L, s_tapB + L.n16b);
   }
 }
 
@@ -681,7 +737,10 @@ __device__ __forceinline__ CPRoute cp_route(const CPGeom& g, const CPBwdLayout& 
 template <bool ONE, bool C1R>
 __device__ __forceinline__ void cp_bwd_body(const CPBwdArgs& a, const int bid, float* smem) {
   const CPGeom& g = a.g;
-  const int b = bid / g.nbands, band = bid % g.nbands;
+  int b, band;
+  a.dNb.divmod(bid, b, band);
+  b = __builtin_amdgcn_readfirstlane(b);                  // (the float divide runs on the VALU)
+  band = __builtin_amdgcn_readfirstlane(band);
   const int pr0 = band * g.PR;
   const CPBand t0 = cp_band(g, 0, 0);
   (void)t0;
@@ -724,8 +783,9 @@ __device__ __forceinline__ void cp_bwd_body(const CPBwdArgs& a, const int bid, f
   const int nX = t.TXH * t.TXW * g.C0;
   const int nC4 = (t.T1H * t.T1W * g.C1 + 3) >> 2;      // the c1 tile in float4s
   float4 cv[CPB_UC];
-  const int C2x2 = 2 * g.C2, sper = CP_THREADS / C2x2;
-  const int scol = (int)threadIdx.x % C2x2, srow = (int)threadIdx.x / C2x2;
+  const int C2x2 = 2 * g.C2, sper = a.sper;
+  int scol, srow;
+  a.dC2x2.divmod((int)threadIdx.x, srow, scol);
   const bool sact = srow < sper;
   float pv[CPB_UP], vf[CPB_US], vb[CPB_US], sc = 0.f, of = 0.f;
   const CPRoute rt = cp_route(g, L, b);
@@ -826,7 +886,9 @@ __device__ __forceinline__ void cp_bwd_body(const CPBwdArgs& a, const int bid, f
     cp_stage_flat(s_wB, a.wB, L.KB * g.C2, L.kpadB * L.c16);
   }
   CP_STAMP(16);
-  for (int i = threadIdx.x; i < L.D2H * L.D2W * g.C2; i += CP_THREADS) s_dc2[i] = 0.f;
+  // (the dc2 tile is a whole number of float4s of the 16-byte aligned carve: 128-bit stores)
+  for (int i = threadIdx.x; i < (L.D2H * L.D2W * g.C2 + 3) >> 2; i += CP_THREADS)
+    reinterpret_cast<float4*>(s_dc2)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
   for (int i = threadIdx.x; i < g.C1; i += CP_THREADS) s_dc1[L.npix1 * g.C1 + i] = 0.f;
   if (!a.tabs) cp_bwd_tables(g, t, L, s_offA, c1r);
   CP_STAMP(17);
@@ -876,7 +938,7 @@ __device__ __forceinline__ void cp_bwd_body(const CPBwdArgs& a, const int bid, f
         ab += srow + u * sper < a.bwd_nslab ? vb[u] : 0.f;
       }
       if ((int)threadIdx.x < 4 * g.C2) {
-        const int k = (int)threadIdx.x / g.C2;
+        const int k = a.dC2.div((int)threadIdx.x);
         s_bn[k * CP_MAXC2 + (int)threadIdx.x - k * g.C2] = sc;
       }
       __syncthreads();                             // the zeroing of s_ss
@@ -941,7 +1003,8 @@ __device__ __forceinline__ void cp_bwd_body(const CPBwdArgs& a, const int bid, f
     const int n = rt.n;
     const float inv_n = a.bn_on ? 1.0f / a.bn.count : 0.f;
     const long base = rt.base;
-    const FastDiv dC(g.C2), dow(ow);
+    const FastDiv& dC = a.dC2;
+    const FastDiv& dow = a.dOw;
     constexpr int U = CP_RU;
     for (int i0 = 0; i0 < n; i0 += CP_THREADS * U) {
       float gz[U], yv[U];
@@ -989,23 +1052,47 @@ __device__ __forceinline__ void cp_bwd_body(const CPBwdArgs& a, const int bid, f
   float* s_bias = s_red + L.n16b * L.c16;                     // [C2] + [C1]
   float* s_rA = smem + L.rA;                                  // [4 waves][16][16] partials
   const bool rA_alias = L.rA == L.dc2;                        // (uniform)
-  cp_gemm(smem, L.n16b >> 4, L.c16 >> 4, L.kp2 >> 2, s_pix2, s_pixd,
-          [&](int m) { return L.c1 + s_tapB[m]; },
-          [&](int n) { return L.dc2 + n; },
-          [&](int tm, int tn, cp_f32x4 acc, int) {
-            const int lane = threadIdx.x & 63, i16 = lane & 15, q = lane >> 4;
+  // Bias gradients (round 9).  No live bias (the sample): nothing.  A live bias whose GEMM
+  // has a spare M row (KB < n16b / KA < 16): that row, fed 1.0, IS the column sum.  Only a
+  // live bias without a spare row keeps the column-sum loop after the barrier below.
+  const int onesB = (a.hasBiasB && L.KB < L.n16b) ? L.KB : -1;
+  const int onesA = (a.bA && L.KA < 16) ? L.KA : -1;
+  const bool loopB = a.hasBiasB && onesB < 0, loopA = a.bA && onesA < 0;   // (uniform, cold)
+  // this wave's units of the dwB + dc1 list (cp_bwd_plan / cp_bwd_plan_dealt)
+  const int* s_plan = s_tapB + L.n16b;
+  const int wv4 = 4 * ((int)threadIdx.x >> 6);
+  const int plB = __builtin_amdgcn_readfirstlane(s_plan[wv4]);
+  const int plT = __builtin_amdgcn_readfirstlane(s_plan[wv4 + 1]);
+  const int plD = __builtin_amdgcn_readfirstlane(s_plan[wv4 + 2]);
+  const int plS = __builtin_amdgcn_readfirstlane(s_plan[wv4 + 3]);
+  {
+    const int ntB = L.c16 >> 4;
+    int tm = plT & 0xffff, tn = plT >> 16;
+    for (int i = plB >> 16; i > 0; --i) {
+      cp_gemm_unit<true>(smem, tm, tn, L.kp2 >> 2, s_pix2, s_pixd,
+                         [&](int m) { return L.c1 + s_tapB[m]; },
+                         [&](int n) { return L.dc2 + n; },
+                         [&](int tm, int tn, cp_f32x4 acc, int) {
+                           const int lane = threadIdx.x & 63, i16 = lane & 15, q = lane >> 4;
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              s_rB[(tm * 16 + 4 * q + r) * L.c16 + tn * 16 + i16] = acc[r];
-            }
-          });
-  // bias B: column sums of the owned dc2 pixels (4 threads per channel + LDS atomics)
-  for (int i = threadIdx.x; i < g.C2 + g.C1; i += CP_THREADS) s_bias[i] = 0.f;
-  CP_STAMP(12);
+                           for (int r = 0; r < 4; ++r) {
+                             s_rB[(tm * 16 + 4 * q + r) * L.c16 + tn * 16 + i16] = acc[r];
+                           }
+                         },
+                         onesB);
+      tn += plS;
+      while (tn >= ntB) { tn -= ntB; ++tm; }
+    }
+  }
+  if (loopA || loopB)
+    for (int i = threadIdx.x; i < g.C2 + g.C1; i += CP_THREADS) s_bias[i] = 0.f;
+  CP_STAMP(12);                                    // (wave 0's dwB units: none under the sample's plan)
   // ---- dc1 of the owned c1 pixels: [pixels] x [C1], K = (i, j, c2), then act A backward
   {
-    const FastDiv dw1(g.W1);
-    cp_gemm(smem, (L.npix1 + 15) >> 4, 1, L.kpadD >> 2, s_offD, s_offW,
+    const FastDiv& dw1 = a.dW1;
+    int tmD = plD & 0xffff;
+    for (int i = plD >> 16; i > 0; --i, tmD += plS)
+      cp_gemm_unit<false>(smem, tmD, 0, L.kpadD >> 2, s_offD, s_offW,
             [&](int m) {
               int yy, xx;
               dw1.divmod(m < L.npix1 ? m : 0, yy, xx);
@@ -1033,34 +1120,40 @@ __device__ __forceinline__ void cp_bwd_body(const CPBwdArgs& a, const int bid, f
   }
   __syncthreads();
   CP_STAMP(13);
-  // bias sums (dc2 over the owned conv-B pixels, dc1 over the owned c1 pixels)
-  {
-    const int per = CP_THREADS / (g.C2 + g.C1);
-    const int col = threadIdx.x % (g.C2 + g.C1), part = threadIdx.x / (g.C2 + g.C1);
+  // bias sums of a bias without a spare GEMM row (dc2 over the owned conv-B pixels, dc1 over
+  // the owned c1 pixels): threads per channel + LDS atomics
+  if (loopA || loopB) {
+    const int per = a.bper;
+    int col, part;
+    a.dBias.divmod((int)threadIdx.x, part, col);
     if (per > 0 && part < per) {
       float acc = 0.f;
       if (col < g.C2) {
-        for (int p = part; p < L.npix2; p += per) acc += s_dc2[s_pixd[p] + col];
-      } else {
+        if (loopB)
+          for (int p = part; p < L.npix2; p += per) acc += s_dc2[s_pixd[p] + col];
+      } else if (loopA) {
         for (int p = part; p < L.npix1; p += per) acc += s_dc1[p * g.C1 + col - g.C2];
       }
       atomicAdd(&s_bias[col], acc);
     }
   }
   // ---- weight gradient A: [taps (i, j, c0)] x [C1], K = owned c1 pixels split over the
-  // 4 waves (partials in LDS)
+  // 4 waves (partials in LDS); row KA fed 1.0 sums dc1 over the pixels (bias A)
   {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i16 = lane & 15, q = lane >> 4;
     const int kst = L.kp1 >> 2, per = (kst + 3) / 4, k0 = wave * per, k1 = min(kst, k0 + per);
     const float* pa = s_x + s_offA[i16 < L.kpadA ? i16 : 0];
     const float* pb = s_dc1 + (i16 < g.C1 ? i16 : 0);
+    const bool one = i16 == onesA;
     cp_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     for (int ks = k0; ks < k1; ++ks) {
       const int p = 4 * ks + q;
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(pa[s_pix1x[p]], pb[s_pix1d[p]], acc, 0, 0, 0);
+      const float av = pa[s_pix1x[p]];
+      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(one ? 1.0f : av, pb[s_pix1d[p]], acc, 0, 0, 0);
     }
-    // the partials overwrite the dc2 tile: every wave's bias sums (its last reader) first
-    if (rA_alias) __syncthreads();
+    // the partials overwrite the dc2 tile: its last readers are the GEMMs before the barrier
+    // above, or the bias loop — every wave's share of it first
+    if (rA_alias && loopB) __syncthreads();
 #pragma unroll
     for (int r = 0; r < 4; ++r) s_rA[wave * 256 + (4 * q + r) * 16 + i16] = acc[r];
   }
@@ -1068,24 +1161,36 @@ __device__ __forceinline__ void cp_bwd_body(const CPBwdArgs& a, const int bid, f
   CP_STAMP(14);
   // ---- one atomic per (workgroup, weight) into stripe blockIdx % S, in memory order
   {
-    const int sidx = bid % a.stripes;
+    int sidx = bid - a.dStripes.div(bid) * a.stripes;
+    sidx = __builtin_amdgcn_readfirstlane(sidx);
     const int nB = L.KB * g.C2;
     for (int o = threadIdx.x; o < nB; o += CP_THREADS) {
-      const int tap = o / g.C2, c2 = o - tap * g.C2;
+      int tap, c2;
+      a.dC2.divmod(o, tap, c2);
       atomicAdd(&a.dwB[(long)sidx * nB + o], s_rB[tap * L.c16 + c2]);
     }
     if (a.hasBiasB)
-      for (int o = threadIdx.x; o < g.C2; o += CP_THREADS) atomicAdd(&a.dbB[(long)sidx * g.C2 + o], s_bias[o]);
+      for (int o = threadIdx.x; o < g.C2; o += CP_THREADS)
+        atomicAdd(&a.dbB[(long)sidx * g.C2 + o], onesB >= 0 ? s_rB[onesB * L.c16 + o] : s_bias[o]);
     const int nA = L.KA * g.C1;
     for (int o = threadIdx.x; o < nA; o += CP_THREADS) {
-      const int tap = o / g.C1, c1 = o - tap * g.C1;
+      int tap, c1;
+      a.dC1.divmod(o, tap, c1);
       float v = 0.f;
 #pragma unroll
       for (int w = 0; w < 4; ++w) v += s_rA[w * 256 + tap * 16 + c1];
       atomicAdd(&a.dwA[(long)sidx * nA + o], v);
     }
     if (a.bA)
-      for (int o = threadIdx.x; o < g.C1; o += CP_THREADS) atomicAdd(&a.dbA[(long)sidx * g.C1 + o], s_bias[g.C2 + o]);
+      for (int o = threadIdx.x; o < g.C1; o += CP_THREADS) {
+        float v = s_bias[g.C2 + o];
+        if (onesA >= 0) {
+          v = 0.f;
+#pragma unroll
+          for (int w = 0; w < 4; ++w) v += s_rA[w * 256 + onesA * 16 + o];
+        }
+        atomicAdd(&a.dbA[(long)sidx * g.C1 + o], v);
+      }
   }
   CP_STAMP(15);
 }
@@ -2162,6 +2267,73 @@ static bool cp_bwd_one_batch(const CPBwdArgs& a) {
   return true;
 }
 
+static void cp_bwd_divs(CPBwdArgs& a) {
+  const CPGeom& g = a.g;
+  a.dNb = FastDiv(g.nbands);
+  a.dStripes = FastDiv(a.stripes);
+  a.dC2x2 = FastDiv(2 * g.C2);
+  a.dC2 = FastDiv(g.C2);
+  a.dC1 = FastDiv(g.C1);
+  a.dOw = FastDiv(g.pool ? g.PW : g.W2);
+  a.dW1 = FastDiv(g.W1);
+  a.dBias = FastDiv(g.C2 + g.C1);
+  a.sper = CP_THREADS / (2 * g.C2);
+  a.bper = CP_THREADS / (g.C2 + g.C1);
+}
+
+static CPBwdLayout cp_bwd_band_layout(const CPGeom& g, int band) {
+  const int pr0 = band * g.PR;
+  const bool last = band == g.nbands - 1;
+  const int o2a = g.pool ? 2 * pr0 : pr0;
+  const int o2b = g.pool ? (last ? g.H2 : 2 * std::min(g.PH, pr0 + g.PR)) : std::min(g.PH, pr0 + g.PR);
+  const CPBand t = cp_band(g, o2a, o2b);
+  return cp_bwd_layout(g, band, t.TXH, t.TXW, t.T1H, t.T1W);
+}
+
+// The unit plan of one band (see CP_PLAN_INTS): the split of nB dwB units (kB k-steps each)
+// and nD dc1 units (kD each) over the four waves with the least busiest wave — exact, by
+// dynamic programming over (waves, units handed out): units of one GEMM are equal, so a
+// wave's share is a pair of counts.  Greedy longest-first gives 48 for the sample's list,
+// the optimum is 42.  on = 0 (no plan emitted) unless it is strictly better than the
+// round-robin dealing, whose busiest wave is `dealt`.
+struct CPPlan { int on, dealt, busiest; int nb[4], nd[4]; int w[CP_PLAN_INTS]; };
+static CPPlan cp_bwd_plan(const CPGeom& g, int band) {
+  CPPlan p{};
+  const CPUnits u = cp_bwd_units(cp_bwd_band_layout(g, band));
+  for (int w = 0; w < 4; ++w) {
+    const int nb = w < u.nB ? (u.nB - w + 3) / 4 : 0, nd = w < u.nD ? (u.nD - w + 3) / 4 : 0;
+    p.dealt = std::max(p.dealt, nb * u.kB + nd * u.kD);
+  }
+  const int SB = u.nB + 1, SD = u.nD + 1;
+  const int INF = 1 << 30;
+  // f[k][i][j]: least busiest wave when k waves took i dwB and j dc1 units
+  std::vector<int> f(5 * SB * SD, INF), cb(5 * SB * SD, 0), cd(5 * SB * SD, 0);
+  auto at = [&](int k, int i, int j) { return (k * SB + i) * SD + j; };
+  f[at(0, 0, 0)] = 0;
+  for (int k = 1; k <= 4; ++k)
+    for (int i = 0; i <= u.nB; ++i)
+      for (int j = 0; j <= u.nD; ++j)
+        for (int bi = 0; bi <= i; ++bi)
+          for (int dj = 0; dj <= j; ++dj) {
+            const int prev = f[at(k - 1, i - bi, j - dj)];
+            if (prev == INF) continue;
+            const int v = std::max(prev, bi * u.kB + dj * u.kD);
+            if (v < f[at(k, i, j)]) { f[at(k, i, j)] = v; cb[at(k, i, j)] = bi; cd[at(k, i, j)] = dj; }
+          }
+  p.busiest = f[at(4, u.nB, u.nD)];
+  if (p.busiest >= p.dealt) return p;
+  for (int k = 4, i = u.nB, j = u.nD; k >= 1; --k) {
+    p.nb[k - 1] = cb[at(k, i, j)]; p.nd[k - 1] = cd[at(k, i, j)];
+    i -= p.nb[k - 1]; j -= p.nd[k - 1];
+  }
+  for (int w = 0, b0 = 0, d0 = 0; w < 4; ++w) {
+    cp_plan_wave(p.w + 4 * w, u.ntB, b0, p.nb[w], d0, p.nd[w], 1);
+    b0 += p.nb[w]; d0 += p.nd[w];
+  }
+  p.on = 1;
+  return p;
+}
+
 static size_t cp_lds(const CPGeom& g, bool bwd) {
   size_t mx = 0;
   for (int band = 0; band < g.nbands; ++band) {
@@ -2479,7 +2651,7 @@ CSA_API int csa_conv_pair_tail_set(unsigned* tk, int* err, int opt, float lr, co
 CSA_API int csa_conv_pair_tail_pending() { return g_cp_tail.on; }
 CSA_API int csa_conv_pair_tail_ticket_words() { return CPT_TK_WORDS; }
 
-__global__ __launch_bounds__(CP_THREADS) void cp_bwd_tables_kernel(CPGeom g, int* out, int stride) {
+__global__ __launch_bounds__(CP_THREADS) void cp_bwd_tables_kernel(CPGeom g, int* out, int stride, CPPlans pl) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int band = blockIdx.x, pr0 = band * g.PR;
   const bool last = band == g.nbands - 1;
@@ -2489,6 +2661,16 @@ __global__ __launch_bounds__(CP_THREADS) void cp_bwd_tables_kernel(CPGeom g, int
   const CPBwdLayout L = cp_bwd_layout(g, band, t.TXH, t.TXW, t.T1H, t.T1W);
   int* s = reinterpret_cast<int*>(smem);
   cp_bwd_tables(g, t, L, s);
+  __syncthreads();
+  // the host's unit plan of this band's class replaces the round-robin record
+  const int cls = last ? 1 : 0;
+  int* s_plan = s + (L.kpadA + 2 * L.kp2 + 2 * L.kpadD + 2 * L.kp1 + L.n16b);
+  if (pl.on[cls] && threadIdx.x < CP_PLAN_INTS) {
+    int v = 0;
+#pragma unroll
+    for (int k = 0; k < CP_PLAN_INTS; ++k) v = (int)threadIdx.x == k ? pl.w[cls][k] : v;
+    s_plan[threadIdx.x] = v;
+  }
   __syncthreads();
   for (int i = threadIdx.x; i < cp_bwd_tab_ints(L); i += CP_THREADS) out[(long)band * stride + i] = s[i];
 }
@@ -2524,9 +2706,63 @@ CSA_API int csa_conv_pair_bwd_tables(const int* geom, int* out, hipStream_t st) 
   CPGeom g;
   if (!cp_geom(geom, g) || !out) return -1;
   const int stride = cp_bwd_tab_stride(g);
+  // every band but the last has the same unit counts: one plan per class
+  CPPlans pl{};
+  for (int cls = 0; cls < 2; ++cls) {
+    if (cls == 0 && g.nbands < 2) continue;
+    const CPPlan p = cp_bwd_plan(g, cls ? g.nbands - 1 : 0);
+    pl.on[cls] = p.on;
+    std::copy(p.w, p.w + CP_PLAN_INTS, pl.w[cls]);
+  }
   hipLaunchKernelGGL(cp_bwd_tables_kernel, dim3((unsigned)g.nbands), dim3(CP_THREADS), (size_t)stride * sizeof(int),
-                     st, g, out, stride);
+                     st, g, out, stride, pl);
   return (int)hipGetLastError();
+}
+
+// The unit plan of a band's dwB + dc1 GEMMs as rows {wave, gemm (0: dwB, 1: dc1), tm, tn,
+// first k-step, end k-step}, each wave's units in the order it runs them.  Returns the
+// number of units, or 0 when no plan is emitted (the round-robin dealing is kept: nothing
+// strictly better exists); out may be null to count.  Runs without a GPU.
+CSA_API int csa_conv_pair_bwd_units(const int* geom, int band, int* out, int cap) {
+  CPGeom g;
+  if (!cp_geom(geom, g) || band < 0 || band >= g.nbands) return -1;
+  const CPPlan p = cp_bwd_plan(g, band);
+  if (!p.on) return 0;
+  const CPUnits u = cp_bwd_units(cp_bwd_band_layout(g, band));
+  int n = 0;
+  for (int w = 0, b0 = 0, d0 = 0; w < 4; ++w) {
+    for (int i = 0; i < p.nb[w] + p.nd[w]; ++i, ++n) {
+      if (!out) continue;
+      if (n >= cap) return -2;
+      const bool isB = i < p.nb[w];
+      const int pr = isB ? b0 + i : d0 + i - p.nb[w];
+      int* r = out + 6 * n;
+      r[0] = w; r[1] = isB ? 0 : 1; r[2] = isB ? pr / u.ntB : pr; r[3] = isB ? pr % u.ntB : 0;
+      r[4] = 0; r[5] = isB ? u.kB : u.kD;
+    }
+    b0 += p.nb[w]; d0 += p.nd[w];
+  }
+  return n;
+}
+
+// {busiest wave of the round-robin dealing, busiest wave of the best split} in k-steps
+CSA_API int csa_conv_pair_bwd_units_load(const int* geom, int band, int* out2) {
+  CPGeom g;
+  if (!cp_geom(geom, g) || band < 0 || band >= g.nbands || !out2) return -1;
+  const CPPlan p = cp_bwd_plan(g, band);
+  out2[0] = p.dealt; out2[1] = p.busiest;
+  return 0;
+}
+
+// Where each bias gradient of the MFMA backward comes from: 0 none (no live bias), 1 the
+// spare M row of its GEMM, 2 the column-sum loop.  Returns modeA | modeB << 4.
+CSA_API int csa_conv_pair_bwd_bias_mode(const int* geom, int hasBiasA, int hasBiasB) {
+  CPGeom g;
+  if (!cp_geom(geom, g)) return -1;
+  const CPBwdLayout L = cp_bwd_band_layout(g, 0);
+  const int mA = !hasBiasA ? 0 : (L.KA < 16 ? 1 : 2);
+  const int mB = !hasBiasB ? 0 : (L.KB < L.n16b ? 1 : 2);
+  return mA | mB << 4;
 }
 
 // The forward BatchNorm tables of the NEXT csa_conv_pair_bwd call (bn_act_apply's [4][C2]
@@ -2558,6 +2794,7 @@ CSA_API int csa_conv_pair_bwd(const int* geom, const uint8_t* img, const int64_t
   a.bn_tab = a.bn_on ? bn_tab : nullptr;
   a.dscale = dscale; a.doffset = doffset; a.run_mean = run_mean; a.run_var = run_var; a.momentum = momentum;
   a.dwA = dwA; a.dbA = dbA; a.dwB = dwB; a.dbB = dbB; a.stripes = stripes < 1 ? 1 : stripes;
+  cp_bwd_divs(a);
   static bool attr = hipFuncSetAttribute((const void*)conv_pair_bwd_kernel<true, false>,
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)CP_LDS_MAX) == hipSuccess &&
                      hipFuncSetAttribute((const void*)conv_pair_bwd_kernel<true, true>,

@@ -129,6 +129,10 @@ _SIGS = {
                               P, P, P, P, I, P, P]),
     "csa_conv_pair_bwd_tables_size": (L, [P]),
     "csa_conv_pair_bwd_tables": (I, [P, P, P]),
+    # round 9: unit plan of the pair backward's dwB + dc1 GEMMs, bias-gradient paths (host only)
+    "csa_conv_pair_bwd_units": (I, [P, I, P, I]),
+    "csa_conv_pair_bwd_units_load": (I, [P, I, P]),
+    "csa_conv_pair_bwd_bias_mode": (I, [P, I, I]),
     "csa_head_part": (I, [P, I, I, I, F, P, P, P, P, P, I, F, P, P, P, P, P, P, P]),
     "csa_head_part2": (I, [P, I, I, I, F, P, P, P, P, P, I, F, P, P, P, P, P, P, P, L, P]),
     "csa_gather_batch": (I, [P, P, P, P, I, L, P, P, P]),
