@@ -13,6 +13,8 @@ Route table (reference views in parentheses):
            POST /construct/construction/<m>/<datatype>/ (ConstructView)
            POST /construct/inference/<m>/ (InferenceView)
   runtime  GET /runtime/train/<m>/<iter>/ (TensorResultView)  GET /runtime/kubernetes/
+           GET /runtime/validation/<m>/ (no reference counterpart: the held-out validation
+           curve and newest confusion matrix of a job run with ``options.eval_every``)
   browser  /login/ /logout/ /password_change/(done/) /password_reset/(done/)
            /reset/<uid>/<token>/ /reset/done/ (django.contrib.auth.urls), /admin/ (api/html_auth.py)
   documented-only in API.md, implemented here: /generation/options/list|next,
@@ -52,7 +54,7 @@ from ..models.options import CATALOG, get_options
 from ..preprocess import ops_ref, pipeline
 from ..runtime.devices import node_status
 from ..runtime.jobs import JobConflict, JobManager
-from ..runtime.trainer import METRICS, RESULT, STATUS, read_train_results
+from ..runtime.trainer import METRICS, RESULT, STATUS, VALIDATION, read_train_results, read_validation
 from ..serve.inference import FAIL_NO_MODEL, InferenceService
 from ..store.db import FILE_TYPES, Database, check_password
 from ..utils import net
@@ -612,6 +614,15 @@ def create_app(settings: Optional[Settings] = None, executor: Optional[str] = No
         if not valid_name(model):
             return J({"detail": "Not found."}, 404)
         return J(read_train_results(os.path.join(settings.model_dir(u["id"], model), RESULT), iters))
+
+    @app.get("/runtime/validation/{model}/")
+    async def validation_results(model: str, request: Request):
+        u, e = need_user(request)
+        if e:
+            return e
+        if not valid_name(model):
+            return J({"detail": "Not found."}, 404)
+        return J(read_validation(os.path.join(settings.model_dir(u["id"], model), VALIDATION)))
 
     @app.get("/runtime/kubernetes/")
     async def kubernetes(request: Request):

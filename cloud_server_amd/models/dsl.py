@@ -309,6 +309,8 @@ class TrainConfig:
     compat_adagrad: bool = False           # True = reference quirk 1 (Adagrad 1e-4)
     sync_bn: bool = False                  # DP: BatchNorm statistics over the GLOBAL batch
     seed: int = 0
+    eval_every: int = 0                    # held-out validation sweep every k steps (0 = off)
+    eval_batch: int = 256                  # rows per validation batch
 
     @property
     def effective_optimizer(self) -> str:
@@ -365,7 +367,13 @@ def parse_train_config(cfg: Union[str, bytes, Dict[str, Any]]) -> TrainConfig:
         compat_adagrad=bool(ext.get("compat_adagrad", False)),
         sync_bn=str(ext.get("sync_bn", False)).lower() in ("1", "true", "yes"),
         seed=_as_int(ext.get("seed", 0), "seed"),
+        eval_every=_as_int(ext.get("eval_every", 0), "eval_every"),
+        eval_batch=_as_int(ext.get("eval_batch", 256), "eval_batch"),
     )
+    if tc.eval_every < 0:
+        raise ConfigError("eval_every must be >= 0")
+    if tc.eval_batch <= 0:
+        raise ConfigError("eval_batch must be > 0")
     if tc.iter < 0:
         raise ConfigError("iter must be >= 0")
     if not (0.0 < tc.ratio <= 1.0):

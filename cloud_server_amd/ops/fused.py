@@ -70,6 +70,10 @@ _SIGS = {
     "csa_head_dgrad": (I, [P, I, I, I, F, P, P, P, P, P, I, F, P, P, P, P, P, P, L, P, I, P, I, F, P, P]),
     "csa_dense_update_flush": (I, [P]),
     "csa_dense_update_clear": (None, []),
+    "csa_eval_rows_fused_ok": (I, [I, I]),
+    "csa_eval_record_ints": (I, []),
+    "csa_eval_rows": (I, [P, I, I, I, F, P, P, P, P, P, P, I, I, I, P, P, P, P]),
+    "csa_eval_finish": (I, [P, P, P, P, I, P, P]),
     "csa_head_row_ok": (I, [I, I]),
     "csa_head_row": (I, [P, I, I, I, F, P, P, P, P, P, I, F, P, P, P, P, P, P, L, P]),
     "csa_head_part_rows": (I, [I, I]),

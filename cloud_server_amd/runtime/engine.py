@@ -494,6 +494,25 @@ class TrainEngine:
         self.model.train()
         return correct / len(ds)
 
+    def validator(self, ds: ArrayDataset, batch: int = 256, predictions: bool = False):
+        """The (cached) validator of ``ds`` at this batch size (``runtime.validation``): the
+        device-resident HIP sweep on the HIP backend, the eager one otherwise."""
+        from .validation import make_validator
+        cache = self.__dict__.setdefault("_validators", {})
+        key = (id(ds), int(batch), bool(predictions))
+        hit = cache.get(key)
+        if hit is None or hit[0] is not ds:
+            hit = cache[key] = (ds, make_validator(self, ds, batch, predictions))
+        return hit[1]
+
+    def validate(self, ds: ArrayDataset, batch: int = 256, predictions: bool = False):
+        """Accuracy, loss and confusion matrix of ``ds`` under the current parameters
+        (``EvalResult``); leaves every piece of training state bit-for-bit unchanged.
+        A host sync: the job loop issues sweeps and drains them without one."""
+        v = self.validator(ds, batch, predictions)
+        v.issue()
+        return v.wait()[1]
+
     def predict_logits(self, x: torch.Tensor) -> torch.Tensor:
         if self.backend == "hip" and hasattr(self.program, "predict_logits"):
             return self.program.predict_logits(x)

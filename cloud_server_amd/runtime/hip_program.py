@@ -1754,6 +1754,19 @@ class HipProgram:
         capturable; ``serve.hip_infer`` captures it per batch bucket).  BatchNorm uses the
         running statistics unless the model normalises with batch statistics in eval
         (``bn_mode == "batch"``), exactly as ``DigitNet.forward`` in eval mode."""
+        hin = self._predict_head_input()
+        Kh = hin.shape[1]
+        if self.lib.csa_dense_fwd_splits(self.B, 10, Kh) > 1:
+            logits.zero_()
+        self._rc(self.lib.csa_dense_fwd(
+            K.ptr(hin), K.ptr(self.views["head.weight"]), K.ptr(self.views["head.bias"]), K.ptr(logits),
+            self.B, 10, Kh, None, 0, 0, 0.0, 0.0, None, None,
+            _act_id(self.head_tf.act), _alpha(self.head_tf.act), K.stream()), "head_fwd")
+
+    def _predict_head_input(self) -> torch.Tensor:
+        """The forward-only pass up to the head's input: returns the last unit's output
+        [B, Kh] BEFORE the head's own activation (``head_tf.act``), which the consumer
+        applies (the logits GEMM above, or ``csa_eval_rows`` in ``runtime.validation``)."""
         st = K.stream()
         self.flush(st)                      # a deferred dense update lands before the forward
         self._eval_bn = self.model.bn_mode != "batch"
@@ -1782,15 +1795,7 @@ class HipProgram:
         finally:
             self._eval_bn = False
             self._predicting = False
-        last = self.units[-1]
-        hin = last.y.view(self.B, -1)
-        Kh = hin.shape[1]
-        if self.lib.csa_dense_fwd_splits(self.B, 10, Kh) > 1:
-            logits.zero_()
-        self._rc(self.lib.csa_dense_fwd(
-            K.ptr(hin), K.ptr(self.views["head.weight"]), K.ptr(self.views["head.bias"]), K.ptr(logits),
-            self.B, 10, Kh, None, 0, 0, 0.0, 0.0, None, None,
-            _act_id(self.head_tf.act), _alpha(self.head_tf.act), st), "head_fwd")
+        return self.units[-1].y.view(self.B, -1)
 
     def _pair_bwd(self, st) -> None:
         e, lib = self.e, self.lib

@@ -38,6 +38,7 @@ RESULT = "result.txt"
 METRICS = "metrics.jsonl"
 STATUS = "status.json"
 CONTROL = "control.json"
+VALIDATION = "validation.jsonl"
 
 
 def write_status(model_dir: str, **fields) -> None:
@@ -241,6 +242,73 @@ class _MetricLog:
             self.fm.close()
 
 
+def _strip_validation_tail(path: str, resume_step: int) -> None:
+    """Drop the rows of ``validation.jsonl`` at or after the step a job resumes from (they
+    are written again as the run passes them), like ``_strip_final_tail``."""
+    if not os.path.exists(path):
+        return
+    keep = []
+    with open(path) as f:
+        for line in f:
+            try:
+                if int(json.loads(line)["step"]) < resume_step:
+                    keep.append(line)
+            except (ValueError, KeyError, TypeError):
+                continue
+    tmp = path + ".tmp"
+    with open(tmp, "w") as f:
+        f.writelines(keep)
+    os.replace(tmp, path)
+
+
+class _ValidationLog:
+    """Held-out validation sweeps (``options.eval_every``) without stalling the device
+    queue: a sweep is issued at a validation point (``runtime.validation``), its result is
+    picked up once its event has completed — normally at a later log or validation point —
+    and the chief appends one line to ``validation.jsonl`` and updates ``status.json``.
+    "Validation at step s" is the parameters after ``s`` updates."""
+
+    def __init__(self, eng: TrainEngine, test: ArrayDataset, chief: bool, model_dir: str):
+        self.eng, self.chief, self.model_dir = eng, chief, model_dir
+        self.path = os.path.join(model_dir, VALIDATION)
+        self.val = eng.validator(test, eng.cfg.eval_batch)
+        self.last_step = -1
+        if chief:
+            _strip_validation_tail(self.path, eng.host_step)
+        self.f = open(self.path, "a") if chief else None
+
+    def issue(self) -> None:
+        step = self.eng.host_step
+        if step == self.last_step:
+            return
+        with trace_range("csa.validate"):
+            self.val.issue(step)
+        self.last_step = step
+        self.drain(block=False)
+
+    def drain(self, block: bool) -> None:
+        wrote = None
+        while True:
+            got = self.val.wait() if block else self.val.poll()
+            if got is None:
+                break
+            step, r = got
+            if self.chief:
+                self.f.write(json.dumps({"step": step, "n": r.n, "loss": r.loss, "accuracy": r.accuracy,
+                                         "confusion": r.confusion, "time": time.time()}) + "\n")
+                wrote = (step, r)
+        if wrote is not None:
+            self.f.flush()
+            write_status(self.model_dir, val_step=wrote[0], val_accuracy=wrote[1].accuracy,
+                         val_loss=wrote[1].loss)
+
+    def close(self) -> None:
+        self.drain(block=True)
+        if self.f is not None:
+            self.f.close()
+            self.f = None
+
+
 class JobRun:
     """One training job's bookkeeping around an engine: resume, logging, heartbeats,
     checkpoints, control actions, fault hooks and the final evaluation.  ``run_job``
@@ -264,6 +332,8 @@ class JobRun:
             write_status(model_dir, state="running", pid=os.getpid(), device=device, world=ctx.world)
         self.ckpter = None
         self.mlog = None
+        self.vlog = None
+        self.val_inloop = False
         try:
             train, self.test = data if data is not None else load_job_data(model_dir, datatype, cfg.ratio)
             self.eng = eng = TrainEngine(cfg, train, device=device, ctx=ctx, backend=backend, packed=packed,
@@ -285,6 +355,17 @@ class JobRun:
             self.ckpter = ckpt.AsyncCheckpointer(eng, model_dir)
             self.mlog = _MetricLog(eng, chief, os.path.join(model_dir, RESULT),
                                    os.path.join(model_dir, METRICS), ctx.world)
+            if cfg.eval_every > 0 and len(self.test):
+                # in-loop sweeps run for one-process jobs driven by run_job; under data
+                # parallelism and in a packed host only the final sweep runs (on every rank,
+                # the chief writes): a chief-only sweep would sit inside the peers' bounded
+                # collective waits
+                self.val_inloop = not ctx.enabled and not packed
+                self.vlog = _ValidationLog(eng, self.test, chief, model_dir)
+                if chief:
+                    write_status(model_dir, validation="in_loop" if self.val_inloop else "final")
+                if self.val_inloop:
+                    self._validate_point()      # a resume AT a validation point re-logs its row
         except Exception as exc:
             self.fail(exc)
             raise
@@ -336,6 +417,9 @@ class JobRun:
             period = self.ctl_every * self.log_every        # comm probe steps run alone
             if any(s % period == 1 for s in range(step, step + k)):
                 return False
+        # a validation point (host_step % eval_every == 0) may only be the END of a group
+        if self.val_inloop and any(s % self.cfg.eval_every == 0 for s in range(step + 1, step + k)):
+            return False
         return (step + k <= self.cfg.iter
                 and all((s % self.log_every) != 0 for s in range(step, step + k - 1))
                 and not (step <= self.fault_at < step + k) and not (step <= self.hang_at < step + k)
@@ -346,6 +430,8 @@ class JobRun:
         state that ends the loop ("stopped" / "paused")."""
         eng = self.eng
         step = eng.host_step - 1
+        if self.val_inloop:
+            self._validate_point()
         if step % self.log_every != 0:
             return ""
         # reference: the accuracy logged for step s is the batch of step s evaluated
@@ -393,15 +479,28 @@ class JobRun:
             return "paused"
         return ""
 
+    def _validate_point(self) -> None:
+        """Issue a sweep when ``host_step`` is a validation point (parameters after that
+        many updates); finished sweeps are written without blocking."""
+        s = self.eng.host_step
+        if s > 0 and s % self.cfg.eval_every == 0:
+            self.vlog.issue()
+        else:
+            self.vlog.drain(block=False)
+
     def finish(self) -> Dict[str, Any]:
         eng, state, chief = self.eng, self.state, self.chief
         eng.finish_async()            # async_ps: drain outstanding pushes, pull final shards
+        if self.vlog is not None and state == "done" and eng.host_step == self.cfg.iter:
+            self.vlog.issue()         # the final sweep (skipped if this step was just validated)
         eng.sync_device()
         # a peer wait that timed out after the last log step left this rank's gradient
         # un-reduced, an in-kernel tail wait skipped updates: fail before evaluating /
         # checkpointing diverged parameters (every rank together under data parallelism)
         eng.check_health()
         self.mlog.close()
+        if self.vlog is not None:
+            self.vlog.close()         # the only blocking drain of validation results
         final_acc = None
         if state == "done":
             final_acc = eng.evaluate(self.test) if len(self.test) else self.mlog.last_acc
@@ -436,6 +535,9 @@ class JobRun:
                 self.ckpter.wait()      # never leave a half-written checkpoint thread behind
         except Exception:
             pass
+        vf = getattr(getattr(self, "vlog", None), "f", None)
+        if vf is not None:
+            vf.close()
         self._unlock()
 
     def _unlock(self) -> None:
@@ -476,6 +578,31 @@ def _agree(ctx: DistContext, action: str) -> str:
     t = torch.tensor([codes.get(action, 0)], device=ctx.device)
     dist.broadcast(t, src=0)
     return {v: k for k, v in codes.items()}[int(t.item())]
+
+
+def read_validation(path: str) -> Dict[str, Any]:
+    """``validation.jsonl`` as the validation route's payload: the curve in
+    ``every_result`` and the newest sweep, with its confusion matrix and per-class recall /
+    precision, in ``latest``.  No file (or no rows): ``{"every_result": []}``."""
+    from .validation import per_class
+    out: Dict[str, Any] = {"every_result": []}
+    if not os.path.exists(path):
+        return out
+    last = None
+    with open(path) as f:
+        for line in f:
+            try:
+                row = json.loads(line)
+                out["every_result"].append({"step": int(row["step"]), "accuracy": row["accuracy"],
+                                            "loss": row["loss"]})
+                last = row
+            except (ValueError, KeyError, TypeError):
+                continue
+    if last is not None:
+        out["latest"] = {"step": int(last["step"]), "n": last.get("n"), "accuracy": last["accuracy"],
+                         "loss": last["loss"], "confusion": last.get("confusion"),
+                         "per_class": per_class(last["confusion"]) if last.get("confusion") else None}
+    return out
 
 
 def read_train_results(path: str, iters: int) -> Dict[str, Any]:
