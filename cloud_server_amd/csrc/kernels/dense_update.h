@@ -88,7 +88,8 @@ namespace csa {
 
 // diagnostics: s_memrealtime stamps (100 MHz, one clock for all XCDs) of EVERY block,
 // [block][16] = start, dY staged, W landed, MFMA + update done, fold done, dX stored, end
-// (update-only bodies: 4 / 5 / 7 / 8 stamp the column halves)
+// (update-only bodies: 4 / 5 / 7 / 8 stamp the column halves; dense_dgrad_kernel: start,
+// first operands landed (1 and 2), MFMA done, fold done, dX stored, end)
 // (scripts/microbench.py MB_DU)
 static __constant__ long long* g_du_dbg = nullptr;   // (per code object)
 #define DU_STAMP(i)                                                                          \
@@ -386,8 +387,11 @@ __device__ __forceinline__ void du_body(const DUArgs& a, const int bid, const in
     }
     // stage dY half j (rows < M only: dgrad rows >= M are clamped reads whose outputs are
     // dropped, wgrad rows >= M meet Xw = 0); its columns are disjoint from half 0's, which
-    // other waves may still be reading.  (UPO: already in LDS; the compiler waits for the
-    // LDS-DMA before the barrier below.)
+    // other waves may still be reading.  (UPO: in LDS once the LDS-DMA has retired.  It is
+    // tracked by vmcnt, which the barrier's own fence need not wait for, so the wait before
+    // the first barrier is explicit: both halves' DMA were issued above, and the other
+    // waves read this wave's rows right after the barrier.)
+    if (UPO && j == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if constexpr (!UPO) {
 #pragma unroll
     for (int u = 0; u < 4; ++u) pin(dyv[j][u]);

@@ -47,6 +47,168 @@ __global__ __launch_bounds__(64 * WAVES) void dense_bwd_update_kernel(DUArgs a) 
   du_body<NSLOT, WAVES, HEAD, DGO>(a, (int)blockIdx.x, (int)gridDim.x, smem);
 }
 
+// ---------------------------------------------------------------------------------------
+// The input gradient alone (round 10): dX[m][f] = sum_n dY[m][n] W[f][n], the forward input
+// transform's backward and the BN-backward statistics, for the wide launch (one workgroup per
+// row group of 16 features, N <= 512, 16 waves).  du_body stages dY in LDS behind a barrier
+// because its weight gradient reads it transposed; the input gradient does not need that:
+//
+//   wave w        the 16-column chunks c = w, w + 16 of every batch tile (as in du_body, so
+//                 every byte of dY and W enters the CU once).
+//   operands      per chunk, lane (i = lane & 15, q = lane >> 4) loads W[f0 + i][16c + 4q ..]
+//                 and, per batch tile t, dY[16t + i][16c + 4q ..] as one float4 each, straight
+//                 from global memory (the MFMA B / A fragments): ten loads issued up front in
+//                 the order they are consumed, so chunk 0's MFMAs run while chunk 1 lands.
+//                 Nothing is staged in LDS, no barrier before the fold.
+//   fold          every wave's tiles meet in LDS as [w][t][r][lane] (one barrier); wave
+//                 (t = w & 3, r = w >> 2) then owns register r of tile t — row 16t + 4q + r of
+//                 feature f0 + i in lane (i, q) — and adds the 16 partials in wave order.
+//   epilogue      one element per lane in all 16 waves: its forward input and its channel's
+//                 4 BN table values were loaded with the operands; a feature's statistics
+//                 fold with 2 shuffles per sum, the waves' rows meet in LDS and fold in wave
+//                 order (exclusive slab row per row group in deterministic mode, one atomic
+//                 per feature and sum otherwise).
+//
+// Rows >= M and features >= nf are computed from clamped (valid) addresses, never stored
+// and never summed.
+constexpr int DG_CH = 2;                                   // chunks per wave (N <= 512)
+constexpr int DG_PART = 16 * 4 * 4 * 64;                   // [w][t][r][lane] partials
+// [partials | BN mean, rstd, a, b | slab-reduction scratch | per-wave statistics [w][2][16]]
+constexpr size_t DG_LDS = (DG_PART + 6 * MAXC_DU + 16 * 32) * sizeof(float);
+
+__global__ __launch_bounds__(1024) void dense_dgrad_kernel(DUArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  float* s_bn = smem + DG_PART;
+  float* s_red = s_bn + 6 * MAXC_DU;
+  const int M = a.M, K = a.K, N = a.N;
+  const int bid = (int)blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int i = lane & 15, q = lane >> 4;
+  const int f0 = bid * DU_FT, nf = min(DU_FT, K - f0);
+  const bool tf = a.act != ACT_NONE || a.bn_on;
+  const bool tabs = a.bn_on && a.bn_tab;
+  const int C = a.bn.C > 0 ? a.bn.C : 1;
+  const int nch = N >> 4;
+  const int et = wave & 3, er = wave >> 2;                 // the epilogue's tile and register
+  DU_STAMP(0);
+
+  // ---- every load, in the order it is consumed (vmcnt retires in order).  Addresses are a
+  // wave-uniform base (the chunk, the row group) plus one 32-bit lane offset per operand
+  const unsigned wo = (unsigned)(min(i, nf - 1) * N + 4 * q) * 4u;
+  unsigned dyo[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) dyo[t] = (unsigned)(min(16 * t + i, M - 1) * N + 4 * q) * 4u;
+  const char* dyb = reinterpret_cast<const char*>(a.dY);
+  const char* wb = reinterpret_cast<const char*>(a.W + (long)f0 * N);
+  float4 dyv[DG_CH][4], wv[DG_CH];
+#pragma unroll
+  for (int u = 0; u < DG_CH; ++u) {
+    const int c = min(wave + 16 * u, nch - 1);             // past the last chunk: a valid one again
+    wv[u] = *reinterpret_cast<const float4*>(wb + 64 * c + wo);
+#pragma unroll
+    for (int t = 0; t < 4; ++t) dyv[u][t] = *reinterpret_cast<const float4*>(dyb + 64 * c + dyo[t]);
+    __builtin_amdgcn_sched_barrier(0);                     // chunk by chunk; the address math below waits
+  }
+  // the epilogue's forward input and BN table values (address selects: unconditional loads)
+  const int ch = (f0 + i) % C;
+  const int em = 16 * et + 4 * q + er;
+  const float* tsrc = tabs ? a.bn_tab : a.dY;
+  float xv = (a.x_fwd ? a.x_fwd : a.dX)[(long)min(em, M - 1) * K + f0 + min(i, nf - 1)];
+  float tb[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) tb[k] = tsrc[tabs ? k * C + ch : 0];
+  if (a.bn_on && !tabs) {                                  // no precomputed tables: reduce here
+    bn_reduce_to_lds(a.bn, s_bn, s_bn + MAXC_DU, s_bn + 2 * MAXC_DU, s_bn + 3 * MAXC_DU, s_bn + 4 * MAXC_DU);
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 4; ++k) tb[k] = s_bn[k * MAXC_DU + ch];
+  }
+
+  // ---- MFMA: A = dY[16t + i][16c + 4q + k], B = W[f0 + i][16c + 4q + k]
+  du_f32x4 acc[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) acc[t] = du_f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int u = 0; u < DG_CH; ++u) {
+    pin(wv[u]);                                            // chunk u has landed (u + 1 may be in flight)
+#pragma unroll
+    for (int t = 0; t < 4; ++t) pin(dyv[u][t]);
+    if (u == 0) { DU_STAMP(1); DU_STAMP(2); }
+    if (wave + 16 * u >= nch) continue;                    // wave-uniform
+    const float wk[4] = {wv[u].x, wv[u].y, wv[u].z, wv[u].w};
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      if (16 * t >= M) break;
+      const float ak[4] = {dyv[u][t].x, dyv[u][t].y, dyv[u][t].z, dyv[u][t].w};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(ak[k], wk[k], acc[t], 0, 0, 0);
+    }
+  }
+  DU_STAMP(3);
+  pin(xv);                                                 // landed long ago; not sunk past the barrier
+#pragma unroll
+  for (int k = 0; k < 4; ++k) pin(tb[k]);
+
+  // ---- fold the waves in fixed order
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    if (16 * t >= M) break;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) smem[((wave * 4 + t) * 4 + r) * 64 + lane] = acc[t][r];
+  }
+  __syncthreads();
+  const bool stats = a.bn_on && a.bwd_slab;
+  const bool live = 16 * et < M;                           // wave-uniform: the tile exists
+  float v1 = 0.f, v2 = 0.f;
+  if (live) {
+    float g = 0.f;
+    const float* src = smem + (et * 4 + er) * 64 + lane;
+#pragma unroll
+    for (int w = 0; w < 16; ++w) g += src[w * 16 * 64];
+    DU_STAMP(4);
+    // ---- transform backward (activation; BN statistics), dX
+    float d2 = 0.f;
+    if (tf) {
+      const float z = a.bn_on ? xv * tb[2] + tb[3] : xv;
+      const float y = act_fwd(z, a.act, a.alpha);
+      g = act_bwd(g, z, y, a.act, a.alpha);
+      d2 = a.bn_on ? g * (xv - tb[0]) * tb[1] : 0.f;
+    }
+    if (em < M && i < nf) {
+      out_store(a.dX + (long)em * K + f0 + i, g);
+      v1 = g;
+      v2 = d2;
+    }
+    DU_STAMP(5);
+  }
+  if (stats) {
+    // a feature's rows of this wave sit in lanes i, i + 16, i + 32, i + 48
+    v1 += __shfl_xor(v1, 16, 64); v2 += __shfl_xor(v2, 16, 64);
+    v1 += __shfl_xor(v1, 32, 64); v2 += __shfl_xor(v2, 32, 64);
+    if (q == 0) { s_red[wave * 32 + i] = v1; s_red[wave * 32 + 16 + i] = v2; }
+    __syncthreads();
+    if (a.det) {
+      // the group's whole row [2][C], features of one channel summed in feature order
+      if (tid < 2 * C) {
+        const int st = tid >= C ? 1 : 0, c = tid - st * C;
+        float sum = 0.f;
+        int cc = f0 % C;
+        for (int ff = 0; ff < nf; ++ff, cc = (cc + 1 == C) ? 0 : cc + 1)
+          if (cc == c)
+            for (int w = 0; w < 16; ++w) sum += s_red[w * 32 + 16 * st + ff];
+        a.bwd_slab[(size_t)bid * 2 * C + tid] = sum;
+      }
+    } else if (tid < 32 && (tid & 15) < nf) {
+      float sum = 0.f;
+#pragma unroll
+      for (int w = 0; w < 16; ++w) sum += s_red[w * 32 + tid];
+      const int st = tid >> 4, c = (f0 + (tid & 15)) % C;
+      atomicAdd(a.bwd_slab + (size_t)(bid % DU_SLAB) * 2 * C + st * C + c, sum);
+    }
+  }
+  DU_STAMP(6);
+}
+
 // Deferred weight-gradient + update segments (see csa_dense_update_defer).
 thread_local DUDeferred g_du_def{};
 
@@ -118,13 +280,13 @@ static void du_launch3(const DUArgs& a, int blocks, hipStream_t st) {
                      du_lds_floats(a.M, WAVES) * sizeof(float), st, a);
 }
 
-template <int WAVES>
-static void du_launch3_dgo(const DUArgs& a, int blocks, hipStream_t st) {
-  static const bool attr = hipFuncSetAttribute((const void*)dense_bwd_update_kernel<0, WAVES, false, true>,
+// dgrad only: the narrow form (column blocks of 128, partial hand-off) stays in du_body
+static void du_launch3_dgo4(const DUArgs& a, int blocks, hipStream_t st) {
+  static const bool attr = hipFuncSetAttribute((const void*)dense_bwd_update_kernel<0, 4, false, true>,
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)DU_LDS_MAX) == hipSuccess;
   (void)attr;
-  hipLaunchKernelGGL((dense_bwd_update_kernel<0, WAVES, false, true>), dim3((unsigned)blocks), dim3(64 * WAVES),
-                     du_lds_floats(a.M, WAVES) * sizeof(float), st, a);
+  hipLaunchKernelGGL((dense_bwd_update_kernel<0, 4, false, true>), dim3((unsigned)blocks), dim3(64 * 4),
+                     du_lds_floats(a.M, 4) * sizeof(float), st, a);
 }
 
 template <int NSLOT, int WAVES>
@@ -260,8 +422,12 @@ CSA_API int csa_dense_bwd_dgrad(const float* dY, const float* W, float* dX, int 
   a.part = part; a.cnt = cnt;
   if (a.cs > 1 && (!part || !cnt)) return -2;
   const int blocks = groups * a.cs;
-  if (a.cs == 1) du_launch3_dgo<16>(a, blocks, st);
-  else du_launch3_dgo<4>(a, blocks, st);
+  if (a.cs == 1) {                                         // one 16-wave workgroup per row group
+    static const bool attr = hipFuncSetAttribute((const void*)dense_dgrad_kernel,
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)DG_LDS) == hipSuccess;
+    (void)attr;
+    hipLaunchKernelGGL(dense_dgrad_kernel, dim3((unsigned)blocks), dim3(1024), DG_LDS, st, a);
+  } else du_launch3_dgo4(a, blocks, st);
   return (int)hipGetLastError();
 }
 

@@ -77,7 +77,7 @@ def main() -> int:
         print(f"  fc1 dgrad  {u_.shape[0]:5d} wg  {span(u_, 0, u_.shape[0], t0)}")
         if uf.shape[0]:
             ph = [(uf[:, k + 1] - uf[:, k]) / 100.0 for k in range(6)]
-            print("     phases mean (us): dY staged {:.2f} | W landed {:.2f} | MFMA {:.2f} | fold {:.2f} | "
+            print("     phases mean (us): operands landed {:.2f} | (stamp) {:.2f} | MFMA {:.2f} | fold {:.2f} | "
                   "transform+dX {:.2f} | BN stats {:.2f}".format(*[float(x.mean()) for x in ph]))
         edges = [0] + [int(x) for x in a.edges.split(",") if x] + [p.shape[0]]
         for lo, hi in zip(edges, edges[1:]):

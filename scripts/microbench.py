@@ -100,8 +100,9 @@ def main() -> int:
                 print(f"{i:2d} {name:18s} conv stamps:", [t[j + 1] - t[j] for j in range(7)])
     if os.environ.get("MB_DU"):
         # per-block stamps (100 MHz realtime): start, loads landed, ticket drawn, finisher end
+        # (the dgrad-only launch: start, first operands landed, -, MFMA, fold, dX stored, end)
         for i, (name, fn, args) in enumerate(rec.calls):
-            if name.startswith("csa_dense_bwd_update"):
+            if name.startswith(("csa_dense_bwd_update", "csa_dense_bwd_dgrad")):
                 grid = 4096
                 dbg = torch.zeros(grid * 16, dtype=torch.int64, device="cuda")
                 for _ in range(3):
