@@ -144,9 +144,6 @@ __device__ __forceinline__ void du_store_w(const DUArgs& a, const float4 (&wv)[D
   }
 }
 
-// NSLOT = optimizer slots (0 SGD, 1 Adagrad, 2 Adam / Adadelta): unused slot registers
-// are not allocated.  WAVES = 16 (one block per row group, all N <= 512 columns) or 4
-// (128 columns per block, cs blocks per row group: narrow layers use more CUs).
 // Head epilogue.  Block (row group grp, column block cblk) owns the dWh rows
 // n in [hn0, hn0 + nh) of its column block (nh = ceil(nb / groups)).  Its operands are tiny
 // — hy[:, hn0 .. hn0 + nh) (M x nh, contiguous per row) and all of dl (M x 10) — and are
@@ -241,6 +238,9 @@ __device__ __forceinline__ void du_head_finish(const DUArgs& a, DUHead& h, float
 
 // One workgroup's work: ``bid`` in [0, nblk) is its index in this layer's grid (a launch
 // that carries the layer beside other work passes its own offset-free numbering).
+// NSLOT = optimizer slots (0 SGD, 1 Adagrad, 2 Adam / Adadelta): unused slot registers
+// are not allocated.  WAVES = 16 (one block per row group, all N <= 512 columns) or 4
+// (128 columns per block, cs blocks per row group: narrow layers use more CUs).
 // DGO (dgrad only): the input gradient + transform backward + BN statistics alone — no
 // weight gradient, no update, no parameter stores (the update runs later in a launch that
 // carries du_body<.., false> workgroups with dX = null beside other work).
@@ -638,8 +638,9 @@ __device__ __forceinline__ void du_body(const DUArgs& a, const int bid, const in
   DU_STAMP(6);
 }
 
-// Extra block e of a carrying launch: the update-only body of its deferred segment
-// (HEADOK = false: the carrier never holds the head segment, its code is not compiled in).
+// Extra block e of a carrying launch: the update-only body of its deferred segment.
+// HEADOK: the head epilogue's code is compiled into the carrier, for the segment u.head (the
+// pair backward carries the head segment and instantiates true).
 // (Measured round 4: fc1's segment riding in the optimizer launch instead ran 0.0906-0.0911
 // ms/step against 0.0885-0.0887 in the pair backward — profiles/r4_notes.md.)
 template <int NSLOT, bool HEADOK>

@@ -217,10 +217,6 @@ thread_local DUDeferred g_du_def{};
 
 using namespace csa;
 
-// gradient-mode outputs of the next launch on this thread (set by csa_dense_bwd_grad_head only)
-static thread_local float* g_du_grad_w = nullptr;
-static thread_local float* g_du_grad_b = nullptr;
-
 CSA_NT_SETTER(csa_nt_out_du)
 
 CSA_API int csa_du_debug(long long* p) {
@@ -271,6 +267,38 @@ CSA_API int csa_dense_bwd_update_ws(int K, int N, long long* ws) {
   return (int)cs;
 }
 
+// DUArgs of one layer from the arguments the entry points share.  The optimizer, gradient-mode
+// and head fields stay zero for the caller to set; scale = 1, cs = what du_cs picks.
+static DUArgs du_args(const float* dY, float* W, float* bias, float* dX, int M, int K, int N, const float* x_fwd,
+                      int act, float alpha, const float* bn_slab, int bn_nslab, int bn_C, float bn_count,
+                      float bn_eps, const float* bn_scale, const float* bn_offset, float* bwd_slab,
+                      const float* Xw, const float* bn_tab, float* part, unsigned* cnt) {
+  DUArgs a{};
+  a.M = M; a.K = K; a.N = N; a.dY = dY; a.W = W; a.bias = bias; a.dX = dX; a.x_fwd = x_fwd;
+  a.act = act; a.alpha = alpha;
+  a.bn = BNRef{bn_slab, bn_nslab, bn_slab ? bn_C : 1, bn_count, bn_eps, bn_scale, bn_offset};
+  a.bn_on = bn_slab != nullptr; a.bn_tab = bn_slab ? bn_tab : nullptr;
+  a.bwd_slab = bwd_slab; a.Xw = Xw; a.det = g_csa_det; a.scale = 1.f;
+  a.cs = du_cs(K, N);
+  a.part = part; a.cnt = cnt;
+  return a;
+}
+
+static void du_optimizer(DUArgs& a, int opt, float lr, const int64_t* step, float* s0w, float* s1w, float* s0b,
+                         float* s1b, float scale) {
+  a.opt = opt; a.lr = lr; a.step = step; a.s0w = s0w; a.s1w = s1w; a.s0b = s0b; a.s1b = s1b; a.scale = scale;
+}
+
+// The head epilogue's arguments (see DUArgs); false when hy is given and another one is missing.
+static bool du_head(DUArgs& a, const float* hy, const float* hdl, float* hgw, float* hgb, const float* hrl,
+                    const int* hrc, float* ring_loss, int* ring_correct, int ring, float ldiv, int hact,
+                    float halpha) {
+  a.hy = hy; a.hdl = hdl; a.hgw = hgw; a.hgb = hgb; a.hrl = hrl; a.hrc = hrc;
+  a.ring_loss = ring_loss; a.ring_correct = ring_correct; a.ring = ring; a.ldiv = ldiv;
+  a.hact = hact; a.halpha = halpha;
+  return !hy || (hdl && hgw && hgb && hrl && hrc && ring_loss && ring_correct && ring >= 1 && a.step);
+}
+
 template <int NSLOT, int WAVES, bool HEAD>
 static void du_launch3(const DUArgs& a, int blocks, hipStream_t st) {
   static const bool attr = hipFuncSetAttribute((const void*)dense_bwd_update_kernel<NSLOT, WAVES, HEAD>,
@@ -280,21 +308,32 @@ static void du_launch3(const DUArgs& a, int blocks, hipStream_t st) {
                      du_lds_floats(a.M, WAVES) * sizeof(float), st, a);
 }
 
-// dgrad only: the narrow form (column blocks of 128, partial hand-off) stays in du_body
-static void du_launch3_dgo4(const DUArgs& a, int blocks, hipStream_t st) {
-  static const bool attr = hipFuncSetAttribute((const void*)dense_bwd_update_kernel<0, 4, false, true>,
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)DU_LDS_MAX) == hipSuccess;
-  (void)attr;
-  hipLaunchKernelGGL((dense_bwd_update_kernel<0, 4, false, true>), dim3((unsigned)blocks), dim3(64 * 4),
-                     du_lds_floats(a.M, 4) * sizeof(float), st, a);
+// Launch the fused backward: the instantiation follows from the block shape (wide: one 16-wave
+// block per row group; else 4-wave column blocks), the optimizer's slots (none in gradient
+// mode) and whether the head epilogue rides along.
+static void du_launch(const DUArgs& a, bool wide, int blocks, hipStream_t st) {
+  using Fn = void (*)(const DUArgs&, int, hipStream_t);
+  static const Fn tab[2][3][2] = {
+      {{du_launch3<0, 4, false>, du_launch3<0, 4, true>},
+       {du_launch3<1, 4, false>, du_launch3<1, 4, true>},
+       {du_launch3<2, 4, false>, du_launch3<2, 4, true>}},
+      {{du_launch3<0, 16, false>, du_launch3<0, 16, true>},
+       {du_launch3<1, 16, false>, du_launch3<1, 16, true>},
+       {du_launch3<2, 16, false>, du_launch3<2, 16, true>}}};
+  tab[wide][a.gW ? 0 : opt_nslots(a.opt)][a.hy != nullptr](a, blocks, st);
 }
 
-template <int NSLOT, int WAVES>
-static void du_launch(const DUArgs& a, int blocks, hipStream_t st) {
-  if (a.hy) du_launch3<NSLOT, WAVES, true>(a, blocks, st);
-  else du_launch3<NSLOT, WAVES, false>(a, blocks, st);
+// One layer's fused backward from its filled arguments: the checks the entry points share.
+static int du_run(const DUArgs& a, bool head_ok, hipStream_t st) {
+  if (!csa_dense_bwd_update_ok(a.M, a.K, a.N, a.bn_on ? a.bn.C : 0)) return -1;
+  if (!head_ok || !a.Xw || !a.W || !a.dY) return -2;
+  if (a.cs > 1 && a.dX && (!a.part || !a.cnt)) return -2;
+  du_launch(a, a.cs == 1, (a.K + DU_FT - 1) / DU_FT * a.cs, st);
+  return (int)hipGetLastError();
 }
 
+// ... plus the head epilogue (hy != null): dWh / dbh of the row-per-workgroup head and the
+// step's metric ring entry are reduced by this launch (see DUArgs).
 CSA_API int csa_dense_bwd_update_head(const float* dY, float* W, float* bias, float* dX, int M, int K, int N,
                                       const float* x_fwd, int act, float alpha, const float* bn_slab, int bn_nslab,
                                       int bn_C, float bn_count, float bn_eps, const float* bn_scale,
@@ -303,7 +342,12 @@ CSA_API int csa_dense_bwd_update_head(const float* dY, float* W, float* bias, fl
                                       float scale, const float* bn_tab, float* part, unsigned* cnt,
                                       const float* hy, const float* hdl, float* hgw, float* hgb, const float* hrl,
                                       const int* hrc, float* ring_loss, int* ring_correct, int ring, float ldiv,
-                                      int hact, float halpha, hipStream_t st);
+                                      int hact, float halpha, hipStream_t st) {
+  DUArgs a = du_args(dY, W, bias, dX, M, K, N, x_fwd, act, alpha, bn_slab, bn_nslab, bn_C, bn_count, bn_eps,
+                     bn_scale, bn_offset, bwd_slab, Xw, bn_tab, part, cnt);
+  du_optimizer(a, opt, lr, step, s0w, s1w, s0b, s1b, scale);
+  return du_run(a, du_head(a, hy, hdl, hgw, hgb, hrl, hrc, ring_loss, ring_correct, ring, ldiv, hact, halpha), st);
+}
 
 CSA_API int csa_dense_bwd_update(const float* dY, float* W, float* bias, float* dX, int M, int K, int N,
                                  const float* x_fwd, int act, float alpha, const float* bn_slab, int bn_nslab,
@@ -315,58 +359,6 @@ CSA_API int csa_dense_bwd_update(const float* dY, float* W, float* bias, float* 
                                    bn_eps, bn_scale, bn_offset, bwd_slab, Xw, opt, lr, step, s0w, s1w, s0b, s1b,
                                    scale, bn_tab, part, cnt, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                                    nullptr, nullptr, 1, 1.f, 0, 0.f, st);
-}
-
-CSA_API int csa_dense_bwd_grad_head(const float* dY, const float* W, float* dX, int M, int K, int N,
-                                    const float* x_fwd, int act, float alpha, const float* bn_slab, int bn_nslab,
-                                    int bn_C, float bn_count, float bn_eps, const float* bn_scale,
-                                    const float* bn_offset, float* bwd_slab, const float* Xw, float scale,
-                                    const float* bn_tab, float* part, unsigned* cnt, float* gW, float* gb,
-                                    const float* hy, const float* hdl, float* hgw, float* hgb, const float* hrl,
-                                    const int* hrc, float* ring_loss, int* ring_correct, int ring, float ldiv,
-                                    int hact, float halpha, const int64_t* step, hipStream_t st);
-
-// ... plus the head epilogue (hy != null): dWh / dbh of the row-per-workgroup head and the
-// step's metric ring entry are reduced by this launch (see DUArgs).
-CSA_API int csa_dense_bwd_update_head(const float* dY, float* W, float* bias, float* dX, int M, int K, int N,
-                                 const float* x_fwd, int act, float alpha, const float* bn_slab, int bn_nslab,
-                                 int bn_C, float bn_count, float bn_eps, const float* bn_scale,
-                                 const float* bn_offset, float* bwd_slab, const float* Xw, int opt, float lr,
-                                 const int64_t* step, float* s0w, float* s1w, float* s0b, float* s1b,
-                                 float scale, const float* bn_tab, float* part, unsigned* cnt,
-                                      const float* hy, const float* hdl, float* hgw, float* hgb, const float* hrl,
-                                      const int* hrc, float* ring_loss, int* ring_correct, int ring, float ldiv,
-                                      int hact, float halpha, hipStream_t st) {
-  if (!csa_dense_bwd_update_ok(M, K, N, bn_slab ? bn_C : 0)) return -1;
-  if (hy && (!hdl || !hgw || !hgb || !hrl || !hrc || !ring_loss || !ring_correct || ring < 1 || !step)) return -2;
-  if (!Xw || !W || !dY) return -2;
-  DUArgs a{};
-  a.M = M; a.K = K; a.N = N; a.dY = dY; a.W = W; a.bias = bias; a.dX = dX; a.x_fwd = x_fwd;
-  a.act = act; a.alpha = alpha;
-  a.bn = BNRef{bn_slab, bn_nslab, bn_slab ? bn_C : 1, bn_count, bn_eps, bn_scale, bn_offset};
-  a.bn_on = bn_slab != nullptr; a.bn_tab = bn_slab ? bn_tab : nullptr;
-  a.bwd_slab = bwd_slab; a.Xw = Xw; a.det = g_csa_det;
-  a.opt = opt; a.lr = lr; a.step = step; a.s0w = s0w; a.s1w = s1w; a.s0b = s0b; a.s1b = s1b; a.scale = scale;
-  const int groups = (K + DU_FT - 1) / DU_FT;
-  a.cs = du_cs(K, N);
-  a.part = part; a.cnt = cnt;
-  a.hy = hy; a.hdl = hdl; a.hgw = hgw; a.hgb = hgb; a.hrl = hrl; a.hrc = hrc;
-  a.ring_loss = ring_loss; a.ring_correct = ring_correct; a.ring = ring; a.ldiv = ldiv;
-  a.hact = hact; a.halpha = halpha;
-  a.gW = g_du_grad_w; a.gb = g_du_grad_b;
-  if (a.cs > 1 && dX && (!part || !cnt)) return -2;
-  const int blocks = groups * a.cs;
-  const int ns = a.gW ? 0 : opt_nslots(opt);
-  if (a.cs == 1) {
-    if (ns == 0) du_launch<0, 16>(a, blocks, st);
-    else if (ns == 1) du_launch<1, 16>(a, blocks, st);
-    else du_launch<2, 16>(a, blocks, st);
-  } else {
-    if (ns == 0) du_launch<0, 4>(a, blocks, st);
-    else if (ns == 1) du_launch<1, 4>(a, blocks, st);
-    else du_launch<2, 4>(a, blocks, st);
-  }
-  return (int)hipGetLastError();
 }
 
 // Data-parallel form: the same fused launch (input gradient + transform backward + BN
@@ -381,15 +373,11 @@ CSA_API int csa_dense_bwd_grad_head(const float* dY, const float* W, float* dX, 
                                     const int* hrc, float* ring_loss, int* ring_correct, int ring, float ldiv,
                                     int hact, float halpha, const int64_t* step, hipStream_t st) {
   if (!gW || !gb) return -2;
-  g_du_grad_w = gW;
-  g_du_grad_b = gb;
-  const int rc = csa_dense_bwd_update_head(dY, const_cast<float*>(W), nullptr, dX, M, K, N, x_fwd, act, alpha,
-                                           bn_slab, bn_nslab, bn_C, bn_count, bn_eps, bn_scale, bn_offset,
-                                           bwd_slab, Xw, OPT_SGD, 0.f, step, nullptr, nullptr, nullptr, nullptr,
-                                           scale, bn_tab, part, cnt, hy, hdl, hgw, hgb, hrl, hrc, ring_loss,
-                                           ring_correct, ring, ldiv, hact, halpha, st);
-  g_du_grad_w = g_du_grad_b = nullptr;
-  return rc;
+  DUArgs a = du_args(dY, const_cast<float*>(W), nullptr, dX, M, K, N, x_fwd, act, alpha, bn_slab, bn_nslab, bn_C,
+                     bn_count, bn_eps, bn_scale, bn_offset, bwd_slab, Xw, bn_tab, part, cnt);
+  du_optimizer(a, OPT_SGD, 0.f, step, nullptr, nullptr, nullptr, nullptr, scale);
+  a.gW = gW; a.gb = gb;
+  return du_run(a, du_head(a, hy, hdl, hgw, hgb, hrl, hrc, ring_loss, ring_correct, ring, ldiv, hact, halpha), st);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -409,25 +397,25 @@ CSA_API int csa_dense_bwd_dgrad(const float* dY, const float* W, float* dX, int 
                                 const float* bn_offset, float* bwd_slab, const float* bn_tab, float* part,
                                 unsigned* cnt, hipStream_t st) {
   if (!csa_dense_bwd_update_ok(M, K, N, bn_slab ? bn_C : 0) || !dX || !dY || !W) return -1;
-  DUArgs a{};
-  a.M = M; a.K = K; a.N = N; a.dY = dY; a.W = const_cast<float*>(W); a.dX = dX; a.x_fwd = x_fwd;
-  a.act = act; a.alpha = alpha;
-  a.bn = BNRef{bn_slab, bn_nslab, bn_slab ? bn_C : 1, bn_count, bn_eps, bn_scale, bn_offset};
-  a.bn_on = bn_slab != nullptr; a.bn_tab = bn_slab ? bn_tab : nullptr;
   // Xw is not read in this mode, but it is the epilogue's address-select fallback for
   // x_fwd, so it must have the [M][K] shape: the input gradient buffer itself
-  a.bwd_slab = bwd_slab; a.Xw = x_fwd ? x_fwd : dX; a.det = g_csa_det; a.scale = 1.f;
-  const int groups = (K + DU_FT - 1) / DU_FT;
-  a.cs = du_cs(K, N);
-  a.part = part; a.cnt = cnt;
+  const DUArgs a = du_args(dY, const_cast<float*>(W), nullptr, dX, M, K, N, x_fwd, act, alpha, bn_slab, bn_nslab,
+                           bn_C, bn_count, bn_eps, bn_scale, bn_offset, bwd_slab, x_fwd ? x_fwd : dX, bn_tab, part,
+                           cnt);
   if (a.cs > 1 && (!part || !cnt)) return -2;
-  const int blocks = groups * a.cs;
+  const unsigned blocks = (unsigned)((K + DU_FT - 1) / DU_FT * a.cs);
   if (a.cs == 1) {                                         // one 16-wave workgroup per row group
     static const bool attr = hipFuncSetAttribute((const void*)dense_dgrad_kernel,
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)DG_LDS) == hipSuccess;
     (void)attr;
-    hipLaunchKernelGGL(dense_dgrad_kernel, dim3((unsigned)blocks), dim3(1024), DG_LDS, st, a);
-  } else du_launch3_dgo4(a, blocks, st);
+    hipLaunchKernelGGL(dense_dgrad_kernel, dim3(blocks), dim3(1024), DG_LDS, st, a);
+  } else {                                 // column blocks of 128, partial hand-off: du_body's dgrad-only form
+    static const bool attr = hipFuncSetAttribute((const void*)dense_bwd_update_kernel<0, 4, false, true>,
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)DU_LDS_MAX) == hipSuccess;
+    (void)attr;
+    hipLaunchKernelGGL((dense_bwd_update_kernel<0, 4, false, true>), dim3(blocks), dim3(256),
+                       du_lds_floats(M, 4) * sizeof(float), st, a);
+  }
   return (int)hipGetLastError();
 }
 
@@ -443,18 +431,14 @@ CSA_API int csa_dense_update_defer(const float* dY, float* W, float* bias, int M
                                    int* ring_correct, int ring, float ldiv, int hact, float halpha) {
   if (!csa_dense_bwd_update_ok(M, K, N, 0) || N % 128 || !Xw || !W || !dY || !step) return -1;
   if (g_du_def.n >= DU_MAXDEF) return -3;
-  if (hy && (g_du_def.head >= 0 || !hdl || !hgw || !hgb || !hrl || !hrc || !ring_loss || !ring_correct || ring < 1))
+  DUArgs a = du_args(dY, W, bias, nullptr, M, K, N, nullptr, 0, 0.f, nullptr, 0, 1, 1.f, 0.f, nullptr, nullptr,
+                     nullptr, Xw, nullptr, nullptr, nullptr);
+  du_optimizer(a, opt, lr, step, s0w, s1w, s0b, s1b, scale);
+  a.cs = N / 128;
+  if (!du_head(a, hy, hdl, hgw, hgb, hrl, hrc, ring_loss, ring_correct, ring, ldiv, hact, halpha) ||
+      (hy && g_du_def.head >= 0))
     return -2;
   if (g_du_def.n > 0 && opt_nslots(g_du_def.seg[0].opt) != opt_nslots(opt)) return -4;   // one NSLOT per launch
-  DUArgs a{};
-  a.M = M; a.K = K; a.N = N; a.dY = dY; a.W = W; a.bias = bias; a.dX = nullptr; a.x_fwd = nullptr;
-  a.bn = BNRef{nullptr, 0, 1, 1.f, 0.f, nullptr, nullptr};
-  a.Xw = Xw; a.det = g_csa_det;
-  a.opt = opt; a.lr = lr; a.step = step; a.s0w = s0w; a.s1w = s1w; a.s0b = s0b; a.s1b = s1b; a.scale = scale;
-  a.cs = N / 128;
-  a.hy = hy; a.hdl = hdl; a.hgw = hgw; a.hgb = hgb; a.hrl = hrl; a.hrc = hrc;
-  a.ring_loss = ring_loss; a.ring_correct = ring_correct; a.ring = ring; a.ldiv = ldiv;
-  a.hact = hact; a.halpha = halpha;
   if (g_du_def.n == 0) g_du_def.head = -1;
   if (hy) g_du_def.head = g_du_def.n;
   g_du_def.blocks[g_du_def.n] = ((K + DU_FT - 1) / DU_FT) * a.cs;
@@ -501,18 +485,11 @@ int du_take(DUSegs& out) {
 }
 }  // namespace csa
 
-// Launch the deferred segments on their own (one 256-thread launch per segment): the
-// fallback when no carrying launch consumed them.
+// Launch the deferred segments on their own (one 256-thread launch of the fused backward per
+// segment, dX = null): the fallback when no carrying launch consumed them.
 namespace csa {
 int du_flush_segs(const DUSegs& u, hipStream_t st) {
-  for (int s = 0; s < u.nseg; ++s) {
-    const DUArgs& a = u.seg[s];
-    const int ns = opt_nslots(a.opt), blocks = u.start[s + 1] - u.start[s];
-    const bool head = s == u.head;
-    if (ns == 0) head ? du_launch3<0, 4, true>(a, blocks, st) : du_launch3<0, 4, false>(a, blocks, st);
-    else if (ns == 1) head ? du_launch3<1, 4, true>(a, blocks, st) : du_launch3<1, 4, false>(a, blocks, st);
-    else head ? du_launch3<2, 4, true>(a, blocks, st) : du_launch3<2, 4, false>(a, blocks, st);
-  }
+  for (int s = 0; s < u.nseg; ++s) du_launch(u.seg[s], false, u.start[s + 1] - u.start[s], st);
   return (int)hipGetLastError();
 }
 }  // namespace csa
