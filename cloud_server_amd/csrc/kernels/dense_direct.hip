@@ -23,6 +23,13 @@
 // Each wave owns a 64-row (two 32-row sub-tiles) x 32-column output tile: the 32x8 B
 // fragment is loaded once for both sub-tiles.  The 4 waves of a workgroup split the
 // workgroup's K range; their partials meet in LDS in fixed wave order.
+//
+// The forward has a second form, dd_fwd_wide_kernel (round 12, further down): 16 waves per
+// workgroup, one 32x32 accumulator per wave, the sixteen partial tiles folded in LDS before
+// anything is emitted, so a launch adds a quarter of the split-K atomic bytes into Y (fc1:
+// 3.03 MB -> 0.78 MB measured).  dd_fwd_plan picks it for the one-process-per-GPU atomic
+// profile; deterministic mode, the packed and the shared-GPU profile, K % 4 != 0, the
+// forward chain and the grouped forward keep dd_fwd_body.
 #include "common.h"
 #include "optim_common.h"
 #include "head_dgrad.h"
@@ -590,6 +597,125 @@ __global__ __launch_bounds__(DD_THREADS) void dd_wgrad_kernel(DDWgrad a) {
   DD_SPAN_END();
 }
 
+// ------------------------------------------------------------------ forward, 16 waves
+// The one-GPU training forward (round 12).  dd_fwd_kernel folds 4 waves before it emits, so
+// fc1 (K = 3920, 31 K slices) added 31 x [50][512] floats into Y with atomics, and global
+// float atomics run at one chip-wide rate whatever issues them.  Here sixteen waves fold on
+// chip first: a quarter of the atomic bytes.
+//
+//   workgroup  1024 threads, one per (32-column tile, 32-row batch block, K slice); the
+//              linear block index is (mb * ksplit + ks) * ntile + nt, so the batch blocks of
+//              one (tile, slice), which read the same W, lie ntile * ksplit blocks apart
+//              (fc1: 128, the same XCD under round-robin placement; for speed only).
+//   wave       a contiguous k range of the slice, a multiple of 8 (fc1: 32 k), ONE 32x32
+//              accumulator.  Fragments and the float4-over-4-steps trick as in dd_fwd_body.
+//              A group (DD_U 8-k blocks) is requested whole before its first MFMA; a further
+//              group of the range lands under the current group's MFMAs.  8-k blocks past
+//              the range are neither loaded nor multiplied; addresses are clamped into the
+//              operands and the terms of a cut last block get B = 0.  Batch rows >= M read a
+//              clamped (valid) row: a row of Y depends on its own row of X only, and those
+//              rows are never written.
+//   fold       the 16 tiles meet in LDS once as [wave][reg][lane] (64 KB, conflict-free both
+//              ways); wave r then sums register r over the waves in wave order, adds the
+//              bias (K slice 0) and emits it: two 128-byte row segments per instruction,
+//              atomicAdd when the launch has more than one K slice, a plain store otherwise.
+//
+// (A wave keeping both 32-row sub-tiles - a 64x32 tile per workgroup, W read once, fc1 as
+// 16 tiles x 16 slices with twice the atomic bytes - was measured slower in the step:
+// 0.0649-0.0652 against 0.0637-0.0639 ms, profiles/r12_notes.md.)
+constexpr int DW_WAVES = 16;
+constexpr int DW_THREADS = 64 * DW_WAVES;
+constexpr size_t DW_LDS = (size_t)DW_WAVES * 16 * 64 * sizeof(float);
+
+struct DWGroup { float4 x[DD_U]; float b[DD_U][4]; };
+
+__global__ __launch_bounds__(DW_THREADS) void dd_fwd_wide_kernel(DDFwd a, int ntile) {
+  extern __shared__ __attribute__((aligned(16))) float s_part[];      // [wave][reg][lane]
+  DD_STAMP(0);
+  DD_SPAN_BEGIN();
+  const int lb = (int)blockIdx.x, tid = threadIdx.x;
+  if (g_dd_life && tid == 0) g_dd_life[2 * lb + 2 * a.life_base] = (long long)__builtin_amdgcn_s_memrealtime();
+  const int lane = tid & 63, i = lane & 31, h = lane >> 5;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int nt = lb % ntile, ks = (lb / ntile) % a.ksplit, mb = lb / (ntile * a.ksplit);
+  const int n0 = nt * 32, m0 = mb * 32;
+  // this wave's k range [ka, kb) inside the slice
+  const int kg0 = ks * a.kper, kg1 = min(a.K, kg0 + a.kper);
+  const int per = (((kg1 - kg0 + 7) >> 3) + DW_WAVES - 1) / DW_WAVES;
+  const int ka = min(kg1, kg0 + wave * per * 8), kb = min(kg1, ka + per * 8);
+  const float* xr = a.x + (long)min(m0 + i, a.M - 1) * a.K;
+  const float* wc = a.w + min(n0 + i, a.N - 1);
+  // the epilogue's bias, requested with the operands (a load issued behind an atomic waits for it)
+  const int er = wave;                                                // the register this wave emits
+  float bias = (a.bias && ks == 0) ? a.bias[min(n0 + i, a.N - 1)] : 0.f;
+
+  auto load = [&](DWGroup& g, int k) {
+#pragma unroll
+    for (int u = 0; u < DD_U; ++u) {
+      if (k + 8 * u >= kb) break;                                     // wave-uniform
+      const int kk = k + 8 * u + 4 * h;                               // K % 4 == 0: kk < K <=> kk <= K - 4
+      g.x[u] = *reinterpret_cast<const float4*>(xr + min(kk, a.K - 4));
+#pragma unroll
+      for (int s = 0; s < 4; ++s) g.b[u][s] = wc[(long)min(kk + s, a.K - 1) * a.N];
+    }
+  };
+  dd_f32x16 acc = {};
+  auto mac = [&](DWGroup& g, int k) {
+#pragma unroll
+    for (int u = 0; u < DD_U; ++u) {
+      if (k + 8 * u >= kb) break;                                     // wave-uniform
+      dd_pin4(g.x[u]);
+#pragma unroll
+      for (int s = 0; s < 4; ++s) dd_pin(g.b[u][s]);
+      float xv[4] = {g.x[u].x, g.x[u].y, g.x[u].z, g.x[u].w};
+      if (a.act != ACT_NONE) {
+#pragma unroll
+        for (int s = 0; s < 4; ++s) xv[s] = act_fwd(xv[s], a.act, a.alpha);
+      }
+      const bool in = k + 8 * u + 4 * h < kb;                         // kb % 4 == 0: one test for the 4 steps
+#pragma unroll
+      for (int s = 0; s < 4; ++s)
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(xv[s], in ? g.b[u][s] : 0.f, acc, 0, 0, 0);
+    }
+  };
+  if (ka < kb) {                                                      // wave-uniform (K slice shorter than 16 ranges)
+    DWGroup cur, nxt;
+    load(cur, ka);
+    for (int k = ka;; k += 8 * DD_U) {
+      if (k + 8 * DD_U < kb) {
+        load(nxt, k + 8 * DD_U);
+        mac(cur, k);
+        cur = nxt;
+      } else {
+        mac(cur, k);
+        break;
+      }
+    }
+  }
+  DD_STAMP(1);
+  dd_pin(bias);
+#pragma unroll
+  for (int r = 0; r < 16; ++r) s_part[(wave * 16 + r) * 64 + lane] = acc[r];
+  __syncthreads();
+  float v = bias;
+  {
+    const float* src = s_part + er * 64 + lane;
+    float s = src[0];
+#pragma unroll
+    for (int w = 1; w < DW_WAVES; ++w) s += src[w * 16 * 64];
+    v += s;
+  }
+  DD_STAMP(2);
+  const int m = m0 + dd_row(er, lane), nn = n0 + i;
+  if (m < a.M && nn < a.N) {
+    float* p = a.y + (long)m * a.N + nn;
+    if (a.ksplit > 1) atomicAdd(p, v); else *p = v;
+  }
+  if (g_dd_life && tid == 0) g_dd_life[2 * lb + 2 * a.life_base + 1] = (long long)__builtin_amdgcn_s_memrealtime();
+  DD_STAMP(3);
+  DD_SPAN_END();
+}
+
 // K slices: enough workgroups for ~1 wave per SIMD (1024), each wave >= 16 k.
 static int dd_splits(int tiles, int K) {
   if (g_csa_det) return 1;                 // deterministic mode: whole-K outputs, plain stores
@@ -608,6 +734,44 @@ static int dd_splits(int tiles, int K) {
 
 static int dd_kper(int K, int ks) { return (((K + ks - 1) / ks) + 7) & ~7; }
 
+// The forward's launch form: dd_fwd_wide_kernel (16-wave workgroups) in the one-process-per-GPU
+// atomic profile, dd_fwd_kernel everywhere else.  Deterministic mode keeps its whole-K 4-wave
+// form (its sums must not move); the packed and the shared-GPU profile keep 256-thread
+// workgroups for the reasons written at du_cs (dense_update.hip).
+//   CSA_DD_WIDE=0: dd_fwd_kernel everywhere (A/B knob)
+//   CSA_DD_WIDE=1: the wide kernel in the packed profile too (A/B knob)
+static bool dd_wide(int K) {
+  static const int wide_env = [] { const char* e = std::getenv("CSA_DD_WIDE"); return e ? (e[0] == '0' ? 0 : 1) : -1; }();
+  if (wide_env == 0 || g_csa_det || g_csa_shared || (g_csa_packed && wide_env != 1)) return false;
+  return K % 4 == 0;
+}
+
+struct DDPlan { bool wide; int ks, kper; };
+
+// K slices of the wide kernel: one workgroup per CU (256) for the shape's tiles, every wave
+// of a slice >= 8 k.  fc1: 16 tiles x 2 batch blocks x 8 slices; fc2 (K = 512): 4 slices,
+// swept in the graph at 1 / 2 / 4 -> workgroup life 4.30 / 2.63 / 2.05 us (dd_fwd_kernel:
+// 3.60), profiles/r12_notes.md.  (CSA_DD_WIDE_KS caps the slices of every wide launch: the
+// A/B knob of that sweep.)
+static DDPlan dd_fwd_plan(int M, int N, int K) {
+  DDPlan p;
+  p.wide = dd_wide(K);
+  if (p.wide) {
+    static const int cap = [] { const char* e = std::getenv("CSA_DD_WIDE_KS"); return e ? std::atoi(e) : 0; }();
+    const int tiles = ((N + 31) / 32) * ((M + 31) / 32);
+    const int maxks = K / (8 * DW_WAVES);
+    p.ks = 256 / tiles;
+    p.ks = p.ks > maxks ? maxks : p.ks;
+    p.ks = cap > 0 && p.ks > cap ? cap : p.ks;
+    p.ks = p.ks < 1 ? 1 : p.ks;
+  } else {
+    p.ks = dd_splits(((N + 31) / 32) * ((M + 63) / 64), K);
+  }
+  p.kper = dd_kper(K, p.ks);
+  p.ks = (K + p.kper - 1) / p.kper;
+  return p;
+}
+
 }  // namespace csa
 
 using namespace csa;
@@ -621,7 +785,14 @@ CSA_API int csa_dd_debug(long long* p) {
 }
 
 CSA_API int csa_dd_fwd_splits(int M, int N, int K) {
-  return dd_splits(((N + 31) / 32) * ((M + 63) / 64), K);
+  if (M <= 0 || N <= 0 || K <= 0) return 1;
+  return dd_fwd_plan(M, N, K).ks;
+}
+
+// 1 when csa_dd_fwd runs this shape as dd_fwd_wide_kernel under the current profile flags
+CSA_API int csa_dd_fwd_wide(int M, int N, int K) {
+  if (M <= 0 || N <= 0 || K <= 0) return 0;
+  return dd_fwd_plan(M, N, K).wide ? 1 : 0;
 }
 
 // Forward chain recording: between csa_chain_begin and csa_chain_end, the two forwards and
@@ -689,9 +860,10 @@ CSA_API int csa_dd_fwd(const float* X, const float* W, const float* bias, float*
                        int act, float alpha, hipStream_t st) {
   if (M <= 0 || N <= 0 || K <= 0) return -1;
   const int nt = (N + 31) / 32, mb = (M + 63) / 64;
-  int ks = dd_splits(nt * mb, K);
-  const int kper = dd_kper(K, ks);
-  ks = (K + kper - 1) / kper;
+  // (a recorded chain or group runs dd_fwd_body with the planned slices: csa_dd_fwd_splits
+  // has told the caller whether Y starts at zero)
+  const DDPlan plan = dd_fwd_plan(M, N, K);
+  const int ks = plan.ks, kper = plan.kper;
   DDFwd a{X, W, bias, Y, M, N, K, act, alpha, ks, kper, 0};
   a.life_base = K > 1024 ? 0 : 4096;                 // (diagnostics: wide layers first)
   if (g_chain_on) {
@@ -704,7 +876,13 @@ CSA_API int csa_dd_fwd(const float* X, const float* W, const float* bias, float*
     g_dd_group.a[g_dd_group.g++] = a;
     return 0;
   }
-  if (K % 4 == 0) hipLaunchKernelGGL(dd_fwd_kernel<true>, dim3(nt, mb, ks), dim3(DD_THREADS), 0, st, a);
+  if (plan.wide) {
+    static const bool attr = hipFuncSetAttribute((const void*)dd_fwd_wide_kernel,
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)DW_LDS) == hipSuccess;
+    (void)attr;
+    const unsigned blocks = (unsigned)(nt * ((M + 31) / 32) * ks);
+    hipLaunchKernelGGL(dd_fwd_wide_kernel, dim3(blocks), dim3(DW_THREADS), DW_LDS, st, a, nt);
+  } else if (K % 4 == 0) hipLaunchKernelGGL(dd_fwd_kernel<true>, dim3(nt, mb, ks), dim3(DD_THREADS), 0, st, a);
   else hipLaunchKernelGGL(dd_fwd_kernel<false>, dim3(nt, mb, ks), dim3(DD_THREADS), 0, st, a);
   return (int)hipGetLastError();
 }

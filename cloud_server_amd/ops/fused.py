@@ -148,6 +148,7 @@ _SIGS = {
     # register-direct MFMA dense kernels (dense_direct.hip)
     "csa_dd_debug": (I, [P]),
     "csa_dd_fwd_splits": (I, [I, I, I]),
+    "csa_dd_fwd_wide": (I, [I, I, I]),
     "csa_dd_fwd": (I, [P, P, P, P, I, I, I, I, F, P]),
     "csa_dd_dgrad_splits": (I, [I, I, I]),
     "csa_dd_dgrad_slabs": (I, []),
