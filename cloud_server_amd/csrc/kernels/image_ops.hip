@@ -13,6 +13,7 @@
 // staged once in LDS; 28x28 digit batches give N workgroups, so a 1k-image batch
 // already fills all 256 CUs several times over.  Elementwise ops are grid-stride.
 #include "common.h"
+#include "crng.h"
 
 // Bit-parity with the NumPy reference: no FMA contraction of the double arithmetic here
 // (the library is built with -ffp-contract=fast-honor-pragmas for the training kernels).
@@ -35,18 +36,7 @@ __device__ __forceinline__ uint8_t sat_rint(double v) {
 }
 
 // ------------------------------------------------------------------ counter RNG
-// Counter-based draws shared bit for bit with ops_ref.crng (NumPy): image i, draw j ->
-// splitmix64(splitmix64((i << 32) | j) ^ seed) >> 32.  No state: every pixel/thread
-// computes its own draw, so the random ops run entirely on the device.
-__device__ __forceinline__ uint64_t smix(uint64_t z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-__device__ __forceinline__ uint32_t crng(uint64_t seed, uint64_t i, uint64_t j) {
-  return (uint32_t)(smix(smix((i << 32) | j) ^ seed) >> 32);
-}
+// smix / crng (crng.h): image i, draw j; every pixel/thread computes its own draw.
 __device__ __forceinline__ double crng_uniform(uint64_t seed, uint64_t i, uint64_t j) {   // [0, 1), 24 bits
   return (double)(crng(seed, i, j) >> 8) * (1.0 / 16777216.0);
 }

@@ -25,7 +25,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .dsl import (ActSpec, ConvSpec, DenseSpec, LayerPlan, NetPlan, NormSpec, PoolSpec,
+from ..ops import dropout_ref
+from .dsl import (ActSpec, ConvSpec, DenseSpec, DropoutSpec, LayerPlan, NetPlan, NormSpec, PoolSpec,
                   TrainConfig)
 
 
@@ -140,6 +141,12 @@ class DigitNet(nn.Module):
         # global too) and every replica normalises with the GLOBAL batch statistics
         self.sync_bn = False
         self.deterministic = False          # CSA_DETERMINISTIC: atomics-free op choices
+        # dropout masks (ops/dropout_ref.py) are a function of (seed, layer, step, element):
+        # the engine hands over its device step counter and its place in the global batch
+        # (``drop_step = eng.dstep``); a model built on its own draws the masks of step 0
+        self.seed = seed
+        self.drop_step = torch.zeros(1, dtype=torch.int64, device=device)
+        self.drop_world, self.drop_rank = 1, 0
         self.state = FlatState(plan.param_shapes(dense_last), device=device, pad_multiple=pad_multiple)
         init_params(plan, self.state, seed)
         self.flat = nn.Parameter(self.state.buffer)
@@ -196,6 +203,14 @@ class DigitNet(nn.Module):
             return F.max_pool2d(t, sp.kernel, sp.stride).permute(0, 2, 3, 1)
         if isinstance(sp, ActSpec):
             return act_fwd(h, sp)
+        if isinstance(sp, DropoutSpec):
+            if not self.training:
+                return h
+            B = h.shape[0]
+            keep = dropout_ref.keep_mask_torch(dropout_ref.drop_seed(self.seed, lp.index), self.drop_step, B,
+                                               h[0].numel(), sp.keep_prob, self.drop_world, self.drop_rank)
+            s = dropout_ref.keep_scale(sp.keep_prob)
+            return h * (keep.view(h.shape).to(h.dtype) * s)
         if isinstance(sp, NormSpec):
             dims = tuple(range(h.dim() - 1))
             scale, offset = self.p(f"{lp.name}.scale"), self.p(f"{lp.name}.offset")

@@ -17,6 +17,9 @@ Reference quirks and how they are handled:
 * ``isBias`` is a string compare against ``"False"`` (construct_distribute.py:228): kept.
 * unknown layer names are skipped silently in the reference; we keep them in the parsed
   config (so ``model.json`` round-trips) but they produce no layer.
+* ``keep_prob`` fed but never used (construct_distribute.py:364-417 feeds 0.5 / 1.0; the
+  ``tf.nn.dropout`` line is a comment, construct_distribute_url.py:328): a ``dropout``
+  layer is a real layer here; a config without one trains without dropout, as before.
 """
 from __future__ import annotations
 
@@ -115,7 +118,13 @@ class NormSpec:
     kind: str = "norm"
 
 
-LayerSpec = Union[ConvSpec, PoolSpec, ActSpec, DenseSpec, NormSpec]
+@dataclass
+class DropoutSpec:
+    keep_prob: float = 0.5                 # the value the reference feeds on training steps
+    kind: str = "dropout"
+
+
+LayerSpec = Union[ConvSpec, PoolSpec, ActSpec, DenseSpec, NormSpec, DropoutSpec]
 
 
 def parse_layer(d: Dict[str, Any], idx: int) -> Optional[LayerSpec]:
@@ -170,6 +179,11 @@ def parse_layer(d: Dict[str, Any], idx: int) -> Optional[LayerSpec]:
         return DenseSpec(h)
     if name == "norm":
         return NormSpec(_as_float(d.get("epsilon", 1e-3), where + ".epsilon"))
+    if name == "dropout":
+        kp = _as_float(d.get("keep_prob", 0.5), where + ".keep_prob")
+        if not (0.0 < kp <= 1.0):
+            raise ConfigError(f"{where}: keep_prob must be in (0, 1]")
+        return DropoutSpec(kp)
     return None  # unknown layers are skipped, as in the reference (:208-250)
 
 
@@ -274,7 +288,7 @@ def plan_network(layers: Sequence[LayerSpec], in_hw: int = INPUT_HW, in_c: int =
             if oh <= 0 or ow <= 0:
                 raise ConfigError(f"layer {i}: pool window larger than its {h}x{w} input")
             plans.append(LayerPlan(i, sp, shape, TensorShape(shape.c, (oh, ow)), (pt, pb, pl, pr)))
-        elif isinstance(sp, ActSpec):
+        elif isinstance(sp, (ActSpec, DropoutSpec)):
             plans.append(LayerPlan(i, sp, shape, shape))
         elif isinstance(sp, NormSpec):
             plans.append(LayerPlan(i, sp, shape, shape, params={"scale": (shape.c,), "offset": (shape.c,)}))

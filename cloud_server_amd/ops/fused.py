@@ -24,6 +24,7 @@ P = C.c_void_p
 I = C.c_int
 L = C.c_long
 F = C.c_float
+U64 = C.c_uint64
 
 ACT_IDS = {None: 0, "none": 0, "sigmoid": 1, "relu": 2, "leaky_relu": 3}
 
@@ -172,7 +173,10 @@ _SIGS = {
     "csa_bn_bwd_apply": (I, [P, P, P, P, L, I, P, P, I, F, P]),
     "csa_maxpool_fwd": (I, [P, P, P, P, P]),
     "csa_maxpool_bwd": (I, [P, P, P, P, P]),
-    "csa_xgmi_alloc": (I, [L, C.POINTER(P), P]),
+    # dropout with counter-RNG masks (dropout.hip; ops/dropout_ref.py is the definition)
+    "csa_drop_fwd": (I, [P, P, L, L, L, L, U64, P, P, I, F, I, F, I, P]),
+    "csa_drop_bwd": (I, [P, P, P, L, L, L, L, U64, P, I, F, I, F, P]),
+    "csa_xgmi_alloc":(I, [L, C.POINTER(P), P]),
     "csa_xgmi_open": (I, [P, C.POINTER(P)]),
     "csa_xgmi_reuse": (I, [P, L, P]),
     "csa_xgmi_close": (I, [P]),

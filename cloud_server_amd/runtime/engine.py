@@ -133,6 +133,9 @@ class TrainEngine:
                                   chunk=stream_chunk, rank=self.ctx.rank, world=self.ctx.world)
         # device-side counters / metric rings (read by host every log interval)
         self.dstep = torch.zeros(1, dtype=torch.int64, device=self.device)
+        # dropout masks are drawn per (step, global batch row): ops/dropout_ref.py
+        self.model.drop_step = self.dstep
+        self.model.drop_world, self.model.drop_rank = self.ctx.world, self.ctx.rank
         self.ring_correct = torch.zeros(RING, dtype=torch.int32, device=self.device)
         self.ring_loss = torch.zeros(RING, dtype=torch.float32, device=self.device)
         self.host_step = 0

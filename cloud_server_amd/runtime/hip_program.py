@@ -29,6 +29,11 @@ follow a conv, act/norm sequences like ``act norm`` — become **standalone unit
 (``norm_pool.hip``): ``bn`` (materialised ``[norm] [act]``: stats -> finalize -> apply,
 with its own backward) and ``pool`` (max pool + gather-form backward).  So every DSL the
 reference accepts (construct_distribute.py:155-165, 208-265) lowers to HIP kernels.
+
+A ``dropout`` layer is a standalone ``drop`` unit (``dropout.hip``): one launch each way,
+the mask redrawn from the counter RNG (ops/dropout_ref.py), never stored.  A lone
+activation in front of it rides in the same launches, so the dense layer after it reads a
+plain tensor.  Forward-only programs skip the layer altogether.
 """
 from __future__ import annotations
 
@@ -40,7 +45,8 @@ from typing import Dict, List, Optional
 
 import torch
 
-from ..models.dsl import ActSpec, ConvSpec, DenseSpec, LayerPlan, NormSpec, PoolSpec
+from ..models.dsl import ActSpec, ConvSpec, DenseSpec, DropoutSpec, LayerPlan, NormSpec, PoolSpec
+from ..ops import dropout_ref
 from ..ops import fused as K
 from ..ops import fused as _FK      # (K is shadowed by feature counts inside _alloc)
 from ..ops import optim_ref
@@ -123,9 +129,9 @@ class Transform:
 
 @dataclass
 class Unit:
-    kind: str                               # "conv" | "dense" | "gconv" | "bn" | "pool"
+    kind: str                               # "conv" | "dense" | "gconv" | "bn" | "pool" | "drop"
     layer: LayerPlan
-    act: Optional[ActSpec] = None           # conv: fused output act
+    act: Optional[ActSpec] = None           # conv: fused output act; bn / drop: applied first
     pool: Optional[LayerPlan] = None        # conv: fused pool
     in_tf: Transform = field(default_factory=Transform)   # transform of this unit's INPUT
     x: Optional[torch.Tensor] = None        # input tensor (pre-transform), None = raw images
@@ -961,6 +967,18 @@ class HipProgram:
                 materialise()                    # pool(act(norm(x))): the transform first
                 units.append(Unit("pool", lp))
                 i += 1
+            elif isinstance(sp, DropoutSpec):
+                i += 1
+                if self.forward_only:
+                    continue                     # identity outside training: no unit, no launch
+                if len(pending) == 1 and isinstance(pending[0].spec, ActSpec):
+                    # a lone activation rides in the drop unit's launches (its backward
+                    # reads the unit's input, so any alpha is fine)
+                    units.append(Unit("drop", lp, act=pending[0].spec))
+                    pending.clear()
+                else:
+                    materialise()
+                    units.append(Unit("drop", lp))
             elif isinstance(sp, (NormSpec, ActSpec)):
                 if isinstance(sp, ActSpec):
                     _act_id(sp)
@@ -999,7 +1017,11 @@ class HipProgram:
                 u.x = (self.x_dense_in if u.kind == "dense" or not ish.is_spatial
                        else self.x_dense_in.view(B, ish.hw[0], ish.hw[1], ish.c))
             lp = u.layer
-            if u.kind == "bn":
+            if u.kind == "drop":
+                u.y = torch.zeros_like(u.x)
+                # the step whose mask the forward drew (the backward redraws that one)
+                u.used_step = torch.zeros(1, dtype=torch.int64, device=dev)
+            elif u.kind == "bn":
                 u.y = torch.zeros_like(u.x)
                 C_ = self._bn_channels(u)
                 if u.norm is not None:
@@ -1427,7 +1449,7 @@ class HipProgram:
                 else:
                     self._grad_ready(0)
                 continue
-            if u.kind in ("bn", "pool"):
+            if u.kind in ("bn", "pool", "drop"):
                 self._standalone_bwd(u, self.units[k - 1] if k > 0 else None, st)
                 self._grad_ready(k)
                 continue
@@ -1606,7 +1628,7 @@ class HipProgram:
         for k, u in enumerate(self.units):
             if self.pair is not None and k < 2:
                 continue
-            if u.kind in ("bn", "pool"):
+            if u.kind in ("bn", "pool", "drop"):
                 self._standalone_fwd(u, st)
                 continue
             if u.kind == "gconv":
@@ -1663,8 +1685,24 @@ class HipProgram:
         return K.ints([self.B, h, w, lp.in_shape.c, sp.kernel[0], sp.kernel[1], sp.stride[0], sp.stride[1],
                        lp.pads[0], lp.pads[2], oh, ow])
 
+    def _drop_args(self, u: Unit):
+        """(n, F, row_mul, row_add, seed) of a drop unit: element (b, f) of this rank's batch
+        draws counter (b * world + rank) * F + f (ops/dropout_ref.py)."""
+        ctx = self.e.ctx
+        return (u.x.numel(), u.x[0].numel(), ctx.world, ctx.rank,
+                dropout_ref.drop_seed(self.e.cfg.seed, u.layer.index))
+
+    def _drop_consts(self, u: Unit):
+        kp = u.layer.spec.keep_prob
+        return (dropout_ref.keep_threshold(kp), dropout_ref.keep_scale(kp), _act_id(u.act), _alpha(u.act))
+
     def _standalone_fwd(self, u: Unit, st) -> None:
         lib = self.lib
+        if u.kind == "drop":
+            train = 0 if getattr(self, "_predicting", False) else 1
+            self._rc(lib.csa_drop_fwd(K.ptr(u.x), K.ptr(u.y), *self._drop_args(u), K.ptr(self.e.dstep),
+                                      K.ptr(u.used_step), *self._drop_consts(u), train, st), "drop_fwd")
+            return
         if u.kind == "pool":
             self._rc(lib.csa_maxpool_fwd(K.ptr(u.x), K.ptr(u.y), K.ptr(u.argmax), self._pool_geom_full(u), st),
                      "maxpool_fwd")
@@ -1717,6 +1755,11 @@ class HipProgram:
     def _standalone_bwd(self, u: Unit, prev: Optional[Unit], st) -> None:
         lib = self.lib
         dx = prev.dy if prev is not None else None
+        if u.kind == "drop":
+            if dx is not None:
+                self._rc(lib.csa_drop_bwd(K.ptr(u.x), K.ptr(u.dy), K.ptr(dx), *self._drop_args(u),
+                                          K.ptr(u.used_step), *self._drop_consts(u), st), "drop_bwd")
+            return
         if u.kind == "pool":
             if dx is not None:
                 self._rc(lib.csa_maxpool_bwd(K.ptr(u.dy), K.ptr(u.argmax), K.ptr(dx), self._pool_geom_full(u), st),
