@@ -29,7 +29,10 @@
 // anything is emitted, so a launch adds a quarter of the split-K atomic bytes into Y (fc1:
 // 3.03 MB -> 0.78 MB measured).  dd_fwd_plan picks it for the one-process-per-GPU atomic
 // profile; deterministic mode, the packed and the shared-GPU profile, K % 4 != 0, the
-// forward chain and the grouped forward keep dd_fwd_body.
+// forward chain and the grouped forward keep dd_fwd_body.  Its BN form, dd_fwd_wide_bn_kernel
+// (round 14, csa_dd_fwd_bn), also applies the producer's BatchNorm + activation to A on load and
+// writes xt, the BatchNorm tables and the carried update's cleared flag: fc1's forward in the
+// one-GPU training program, where bn_act_apply (elementwise.hip) was a launch of its own.
 #include "common.h"
 #include "optim_common.h"
 #include "head_dgrad.h"
@@ -63,6 +66,19 @@ __constant__ long long* g_dd_dbg = nullptr;
     if (g_dd_dbg && threadIdx.x == 0)                                                         \
       atomicMax((unsigned long long*)&g_dd_dbg[5], (unsigned long long)__builtin_amdgcn_s_memtime()); \
   } while (0)
+
+// diagnostic build only (-DCSA_DD_PHASES): phase p of every workgroup of the BN forward at
+// [8 + 8 b + p] (s_memrealtime, 100 MHz): 0 start | 1 table in LDS, barrier passed | 2 X landed |
+// 3 transform done | 4 W landed | 5 MFMAs issued, xt stores out (scripts/mb/graph_life.py)
+#ifdef CSA_DD_PHASES
+#define DD_PHASE(p)                                                                           \
+  do {                                                                                        \
+    if (g_dd_dbg && threadIdx.x == 0)                                                         \
+      g_dd_dbg[8 + 8 * (int)blockIdx.x + (p)] = (long long)__builtin_amdgcn_s_memrealtime();  \
+  } while (0)
+#else
+#define DD_PHASE(p) do {} while (0)
+#endif
 
 __device__ __forceinline__ int dd_row(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
 
@@ -125,7 +141,12 @@ __constant__ long long* g_dd_life = nullptr;
 
 // (Applying a producer's BatchNorm while loading A — from its statistic slab, or from a
 // table the conv pair's last workgroup folded — was measured slower than the separate
-// bn_act_apply launch both times: profiles/r2_dense_direct.md, profiles/r3_notes.md.)
+// bn_act_apply launch in this 4-wave form, three times: profiles/r2_dense_direct.md,
+// profiles/r3_notes.md.  The fourth attempt, on the 16-wave forward below
+// (dd_fwd_wide_bn_kernel, round 14), is faster than the two launches: 10.3 us against
+// 5.5 + 6.5 in the kernel trace, the step 1.8 % shorter — less than the launch boundary and
+// bn_act_apply's span together, because the fused workgroup lives 7.2 us where the plain one
+// lives 4.6: profiles/r14_notes.md.)
 template <bool V4>
 __device__ __forceinline__ void dd_fwd_body(const DDFwd& a, const int nt, const int mb, const int ks, float* s_red);
 
@@ -629,8 +650,33 @@ constexpr size_t DW_LDS = (size_t)DW_WAVES * 16 * 64 * sizeof(float);
 
 struct DWGroup { float4 x[DD_U]; float b[DD_U][4]; };
 
-__global__ __launch_bounds__(DW_THREADS) void dd_fwd_wide_kernel(DDFwd a, int ntile) {
-  extern __shared__ __attribute__((aligned(16))) float s_part[];      // [wave][reg][lane]
+// The BN form (round 14): X is the producer's raw output, and the launch applies
+// xt = act(x * a[c] + b[c]), c = k % C, to the A fragments in registers, where bn_act_apply was
+// a launch of its own in front of this one.
+//   table      2C threads (lanes 2c, 2c + 1: sum x, sum x^2 of channel c) ask for their slab column
+//              BEFORE the operand loads (loads return in order: behind them the fold would wait
+//              for W) and add the rows in row order; the even lane derives mean / rstd / a / b
+//              with bn_reduce_to_lds's formulas and writes them to LDS; ONE barrier, the operand
+//              loads in flight across it.  No atomics: every workgroup of the launch derives the
+//              same bits, so the sixteen column tiles that transform an element agree with the
+//              one that stores it.
+//   transform  a whole load group in registers before its MFMAs; X is requested ahead of W so
+//              the transform runs under W's flight.  The channel of a lane's first k comes from
+//              one FastDiv, then add-and-wrap.
+//   xt         every column tile holds the same (batch block, K slice, wave) chunk: tile nt
+//              stores the chunks of the waves w with w % min(ntile, 16) == nt, after the group's
+//              MFMAs, rows < M and k < K only.
+//   tab, flag  workgroup 0 writes [4][C] mean | rstd | a | b and zeroes the pending flag, as
+//              bn_act_apply's block 0 did.
+struct DDFwdBN {
+  BNRef bn; float* xt; float* tab; unsigned* clear;
+  FastDiv dc; int step8;                                              // k % C; 8 % C
+};
+constexpr int DW_SU = 32;                                             // slab rows in flight per thread
+
+template <bool BN>
+__device__ __forceinline__ void dd_fwd_wide_body(DDFwd a, int ntile, const DDFwdBN q, float* s_part,
+                                                 float2* s_ab, float* s_mr) {
   DD_STAMP(0);
   DD_SPAN_BEGIN();
   const int lb = (int)blockIdx.x, tid = threadIdx.x;
@@ -649,6 +695,29 @@ __global__ __launch_bounds__(DW_THREADS) void dd_fwd_wide_kernel(DDFwd a, int nt
   const int er = wave;                                                // the register this wave emits
   float bias = (a.bias && ks == 0) ? a.bias[min(n0 + i, a.N - 1)] : 0.f;
 
+  // BN: this thread's slab column (the last DW_SU rows stay in flight across the operand loads)
+  float sv[DW_SU], ssum = 0.f, sco = 0.f;
+  int srow = 0;
+  const int C = BN ? q.bn.C : 1;
+  if constexpr (BN) {
+    if (tid < 2 * C) {
+      const int c = tid >> 1;
+      sco = (tid & 1) ? q.bn.offset[c] : q.bn.scale[c];
+      const float* col = q.bn.slab + (tid & 1) * C + c;
+      for (; srow + DW_SU < q.bn.nslab; srow += DW_SU) {              // (slabs of more than DW_SU rows)
+#pragma unroll
+        for (int u = 0; u < DW_SU; ++u) sv[u] = col[(size_t)(srow + u) * 2 * C];
+#pragma unroll
+        for (int u = 0; u < DW_SU; ++u) dd_pin(sv[u]);
+#pragma unroll
+        for (int u = 0; u < DW_SU; ++u) ssum += sv[u];
+      }
+#pragma unroll
+      for (int u = 0; u < DW_SU; ++u) sv[u] = col[(size_t)min(srow + u, q.bn.nslab - 1) * 2 * C];
+    }
+    asm volatile("" ::: "memory");                                    // the operands are requested behind these
+  }
+
   auto load = [&](DWGroup& g, int k) {
 #pragma unroll
     for (int u = 0; u < DD_U; ++u) {
@@ -658,6 +727,17 @@ __global__ __launch_bounds__(DW_THREADS) void dd_fwd_wide_kernel(DDFwd a, int nt
 #pragma unroll
       for (int s = 0; s < 4; ++s) g.b[u][s] = wc[(long)min(kk + s, a.K - 1) * a.N];
     }
+  };
+  // BN: a whole group whatever the range (addresses are clamped into the operands), X ahead
+  // of W: a fixed number of loads behind the slab's, so the fold waits for the slab alone
+  auto load_all = [&](DWGroup& g, int k) {
+#pragma unroll
+    for (int u = 0; u < DD_U; ++u)
+      g.x[u] = *reinterpret_cast<const float4*>(xr + min(k + 8 * u + 4 * h, a.K - 4));
+#pragma unroll
+    for (int u = 0; u < DD_U; ++u)
+#pragma unroll
+      for (int s = 0; s < 4; ++s) g.b[u][s] = wc[(long)min(k + 8 * u + 4 * h + s, a.K - 1) * a.N];
   };
   dd_f32x16 acc = {};
   auto mac = [&](DWGroup& g, int k) {
@@ -678,7 +758,120 @@ __global__ __launch_bounds__(DW_THREADS) void dd_fwd_wide_kernel(DDFwd a, int nt
         acc = __builtin_amdgcn_mfma_f32_32x32x2f32(xv[s], in ? g.b[u][s] : 0.f, acc, 0, 0, 0);
     }
   };
-  if (ka < kb) {                                                      // wave-uniform (K slice shorter than 16 ranges)
+  // BN: the group's X becomes xt in place (terms outside the range: 0), then the MFMA chain
+  int cu = 0;                                                         // channel of this lane's next 8-k block
+  auto mac_bn = [&](DWGroup& g, int k) {
+#pragma unroll
+    for (int u = 0; u < DD_U; ++u) dd_pin4(g.x[u]);
+    DD_PHASE(2);
+    // (branch-free over the whole group: a block past the range holds clamped, valid data)
+    float z[DD_U][4];
+#pragma unroll
+    for (int u = 0; u < DD_U; ++u) {
+      int c = cu;
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        const float2 ab = s_ab[c];
+        z[u][s] = dd_c(g.x[u], s) * ab.x + ab.y;
+        c = (c + 1 == C) ? 0 : c + 1;
+      }
+      cu += q.step8;
+      cu = cu >= C ? cu - C : cu;
+    }
+    // one branch on the activation for the group (act_fwd's own switch, per value, is a
+    // chain of scalar branches in front of every v_exp)
+#define DD_ACT_GROUP(ACT)                                                                     \
+  _Pragma("unroll") for (int u = 0; u < DD_U; ++u)                                            \
+  _Pragma("unroll") for (int s = 0; s < 4; ++s) z[u][s] = act_fwd(z[u][s], ACT, a.alpha)
+    switch (a.act) {
+      case ACT_SIGMOID: DD_ACT_GROUP(ACT_SIGMOID); break;
+      case ACT_RELU: DD_ACT_GROUP(ACT_RELU); break;
+      case ACT_LEAKY: DD_ACT_GROUP(ACT_LEAKY); break;
+      default: break;
+    }
+#undef DD_ACT_GROUP
+#pragma unroll
+    for (int u = 0; u < DD_U; ++u) {
+      const bool in = k + 8 * u + 4 * h < kb;
+#pragma unroll
+      for (int s = 0; s < 4; ++s) dd_pin(z[u][s]);
+      g.x[u] = make_float4(in ? z[u][0] : 0.f, in ? z[u][1] : 0.f, in ? z[u][2] : 0.f, in ? z[u][3] : 0.f);
+    }
+    DD_PHASE(3);
+#ifdef CSA_DD_PHASES
+#pragma unroll
+    for (int u = 0; u < DD_U; ++u)
+#pragma unroll
+      for (int s = 0; s < 4; ++s) dd_pin(g.b[u][s]);
+    DD_PHASE(4);
+#endif
+#pragma unroll
+    for (int u = 0; u < DD_U; ++u) {
+      if (k + 8 * u >= kb) break;                                     // wave-uniform
+#pragma unroll
+      for (int s = 0; s < 4; ++s) dd_pin(g.b[u][s]);
+      const bool in = k + 8 * u + 4 * h < kb;
+#pragma unroll
+      for (int s = 0; s < 4; ++s)
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(dd_c(g.x[u], s), in ? g.b[u][s] : 0.f, acc, 0, 0, 0);
+    }
+  };
+  if constexpr (BN) {
+    DWGroup cur, nxt;
+    DD_PHASE(0);
+    load_all(cur, ka);
+    // the table: rows in row order, lanes 2c / 2c + 1 meet, the even lane derives channel c
+    if (tid < 2 * C) {
+#pragma unroll
+      for (int u = 0; u < DW_SU; ++u) dd_pin(sv[u]);
+#pragma unroll
+      for (int u = 0; u < DW_SU; ++u) ssum += srow + u < q.bn.nslab ? sv[u] : 0.f;
+    }
+    const float osum = __shfl_xor(ssum, 1, 64), oco = __shfl_xor(sco, 1, 64);
+    if (tid < 2 * C && !(tid & 1)) {
+      const int c = tid >> 1;
+      float mean = ssum / q.bn.count;
+      float var = fmaxf(osum / q.bn.count - mean * mean, 0.f);
+      float rstd = rsqrtf(var + q.bn.eps);
+      float sa = sco * rstd;
+      s_mr[c] = mean;
+      s_mr[DD_MAXC + c] = rstd;
+      s_ab[c] = make_float2(sa, oco - mean * sa);
+    }
+    __syncthreads();
+    DD_PHASE(1);
+    if (lb == 0) {
+      if (q.clear && tid == 0) *q.clear = 0u;
+      if (q.tab && tid < C) {
+        const float2 ab = s_ab[tid];
+        q.tab[tid] = s_mr[tid];
+        q.tab[C + tid] = s_mr[DD_MAXC + tid];
+        q.tab[2 * C + tid] = ab.x;
+        q.tab[3 * C + tid] = ab.y;
+      }
+    }
+    int qq;
+    q.dc.divmod(ka + 4 * h, qq, cu);
+    // this wave's chunk of xt goes out from one column tile
+    const bool put_ok = nt == wave % min(ntile, DW_WAVES) && m0 + i < a.M;
+    float* xo = q.xt + (long)min(m0 + i, a.M - 1) * a.K;
+    auto put = [&](DWGroup& g, int k) {
+#pragma unroll
+      for (int u = 0; u < DD_U; ++u) {
+        if (k + 8 * u >= kb) break;                                   // wave-uniform
+        const int kk = k + 8 * u + 4 * h;
+        if (put_ok && kk < kb) *reinterpret_cast<float4*>(xo + kk) = g.x[u];
+      }
+    };
+    for (int k = ka; k < kb; k += 8 * DD_U) {
+      const bool more = k + 8 * DD_U < kb;                            // wave-uniform
+      if (more) load_all(nxt, k + 8 * DD_U);
+      mac_bn(cur, k);
+      put(cur, k);
+      DD_PHASE(5);
+      if (more) cur = nxt;
+    }
+  } else if (ka < kb) {                                               // wave-uniform (K slice shorter than 16 ranges)
     DWGroup cur, nxt;
     load(cur, ka);
     for (int k = ka;; k += 8 * DD_U) {
@@ -714,6 +907,18 @@ __global__ __launch_bounds__(DW_THREADS) void dd_fwd_wide_kernel(DDFwd a, int nt
   if (g_dd_life && tid == 0) g_dd_life[2 * lb + 2 * a.life_base + 1] = (long long)__builtin_amdgcn_s_memrealtime();
   DD_STAMP(3);
   DD_SPAN_END();
+}
+
+__global__ __launch_bounds__(DW_THREADS) void dd_fwd_wide_kernel(DDFwd a, int ntile) {
+  extern __shared__ __attribute__((aligned(16))) float s_part[];      // [wave][reg][lane]
+  dd_fwd_wide_body<false>(a, ntile, DDFwdBN{}, s_part, nullptr, nullptr);
+}
+
+__global__ __launch_bounds__(DW_THREADS) void dd_fwd_wide_bn_kernel(DDFwd a, int ntile, DDFwdBN q) {
+  extern __shared__ __attribute__((aligned(16))) float s_part[];      // [wave][reg][lane]
+  __shared__ float2 s_ab[DD_MAXC];                                    // (a, b) of channel c
+  __shared__ float s_mr[2 * DD_MAXC];                                 // mean | rstd
+  dd_fwd_wide_body<true>(a, ntile, q, s_part, s_ab, s_mr);
 }
 
 // K slices: enough workgroups for ~1 wave per SIMD (1024), each wave >= 16 k.
@@ -884,6 +1089,38 @@ CSA_API int csa_dd_fwd(const float* X, const float* W, const float* bias, float*
     hipLaunchKernelGGL(dd_fwd_wide_kernel, dim3(blocks), dim3(DW_THREADS), DW_LDS, st, a, nt);
   } else if (K % 4 == 0) hipLaunchKernelGGL(dd_fwd_kernel<true>, dim3(nt, mb, ks), dim3(DD_THREADS), 0, st, a);
   else hipLaunchKernelGGL(dd_fwd_kernel<false>, dim3(nt, mb, ks), dim3(DD_THREADS), 0, st, a);
+  return (int)hipGetLastError();
+}
+
+// 1 when csa_dd_fwd_bn takes this shape: it runs wide under the calling thread's profile flags
+// and the producer's channels divide K (channel of k = k % C, NHWC flattened).
+CSA_API int csa_dd_fwd_bn_ok(int M, int N, int K, int C) {
+  if (M <= 0 || N <= 0 || K <= 0 || C <= 0 || C > DD_MAXC) return 0;
+  if (K % 4 != 0 || K % C != 0) return 0;
+  return dd_fwd_plan(M, N, K).wide ? 1 : 0;
+}
+
+// csa_bn_act_apply + csa_dd_fwd in one launch (dd_fwd_wide_bn_kernel):
+//   xt[M][K] = act(X * a[c] + b[c]), Y[M][N] (+)= xt . W + bias
+// with (a, b) from the BatchNorm forward slab; tab (optional) gets [4][C] mean | rstd | a | b,
+// *clear (optional: the carried update's pending flag) gets 0.  Y zeroed when splits > 1.
+// Never part of a recorded chain or group.
+CSA_API int csa_dd_fwd_bn(const float* X, const float* W, const float* bias, float* Y, int M, int N, int K,
+                          int C, const float* bn_slab, int bn_nslab, float bn_count, float bn_eps,
+                          const float* bn_scale, const float* bn_offset, int act, float alpha,
+                          float* xt, float* tab, unsigned* clear, hipStream_t st) {
+  if (!csa_dd_fwd_bn_ok(M, N, K, C) || !X || !xt || !bn_slab || bn_nslab <= 0 || !bn_scale || !bn_offset) return -1;
+  if (g_chain_on || g_dd_grouping) return -5;
+  const DDPlan plan = dd_fwd_plan(M, N, K);
+  DDFwd a{X, W, bias, Y, M, N, K, act, alpha, plan.ks, plan.kper, 0};
+  a.life_base = K > 1024 ? 0 : 4096;                 // (diagnostics: wide layers first)
+  DDFwdBN q{BNRef{bn_slab, bn_nslab, C, bn_count, bn_eps, bn_scale, bn_offset}, xt, tab, clear, FastDiv(C), 8 % C};
+  static const bool attr = hipFuncSetAttribute((const void*)dd_fwd_wide_bn_kernel,
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)DW_LDS) == hipSuccess;
+  (void)attr;
+  const int nt = (N + 31) / 32;
+  const unsigned blocks = (unsigned)(nt * ((M + 31) / 32) * plan.ks);
+  hipLaunchKernelGGL(dd_fwd_wide_bn_kernel, dim3(blocks), dim3(DW_THREADS), DW_LDS, st, a, nt, q);
   return (int)hipGetLastError();
 }
 

@@ -6,6 +6,13 @@
 // so the GEMM prologues of its forward and weight-gradient launches stream plain float4
 // operands instead of recomputing BN + sigmoid per N-tile (measured: the recompute made
 // those GEMMs VALU-bound).
+//
+// In the one-GPU training program this launch no longer runs for fc1: its forward
+// (dense_direct.hip dd_fwd_wide_bn_kernel, csa_dd_fwd_bn) applies the transform to its A
+// fragments in registers and stores xt, the [4][C] tables and the cleared pending flag itself.
+// csa_bn_act_apply still materialises xt in the deterministic, the packed and the shared-GPU
+// profile, for K % 4 != 0 or K % C != 0, in front of the LDS-staged GEMM, the forward chain and
+// the grouped forward, in serving programs and under CSA_FWD_BN_FUSE=0.
 #include "common.h"
 
 namespace csa {

@@ -151,6 +151,10 @@ _SIGS = {
     "csa_dd_fwd_splits": (I, [I, I, I]),
     "csa_dd_fwd_wide": (I, [I, I, I]),
     "csa_dd_fwd": (I, [P, P, P, P, I, I, I, I, F, P]),
+    # the wide forward with the producer's BatchNorm + activation applied on load (xt, the
+    # tables and the pending-flag word written by the same launch)
+    "csa_dd_fwd_bn_ok": (I, [I, I, I, I]),
+    "csa_dd_fwd_bn": (I, [P, P, P, P, I, I, I, I, P, I, F, F, P, P, I, F, P, P, P, P]),
     "csa_dd_dgrad_splits": (I, [I, I, I]),
     "csa_dd_dgrad_slabs": (I, []),
     "csa_dd_dgrad": (I, [P, P, P, I, I, I, P, I, F, P, I, I, F, F, P, P, P, P]),

@@ -213,6 +213,7 @@ class HipProgram:
             self._check_det()
         self._alloc()
         self._plan_splits()
+        self._plan_fwd_bn()
         # the pair backward's per-band index tables, computed once (csa_conv_pair_bwd_tables)
         self.pair_tabs = None
         if self.pair is not None and not forward_only:
@@ -261,6 +262,8 @@ class HipProgram:
         self.chain_tk = torch.zeros(int(self.lib.csa_chain_words()), dtype=torch.int32, device=e.device)
         self.chain_err = torch.zeros(1, dtype=torch.int32, device=e.device)
         self.chain = True
+        for u in dense:                     # the chain records csa_dd_fwd: bn_act_apply stays a launch
+            u.fwd_bn = False
 
     # ------------------------------------------------------------------ DP deferred update
     def _plan_carry(self) -> None:
@@ -1137,6 +1140,29 @@ class HipProgram:
             elif u.kind == "gconv":
                 u.splits_fwd = self.lib.csa_gconv_fwd_splits(self._conv_geom(u.layer, B))
 
+    def _plan_fwd_bn(self) -> None:
+        """Dense units whose forward applies the producer's BatchNorm + activation itself
+        (``csa_dd_fwd_bn``: xt, the BatchNorm tables and the carried update's pending flag come
+        out of the forward's launch) instead of a ``csa_bn_act_apply`` launch in front of
+        ``csa_dd_fwd``: a register-direct unit with xt whose shape runs as the wide kernel and
+        whose K is a multiple of the producer's channels.  Serving programs, the forward chain
+        and a baseline library without the entry point keep the two launches;
+        ``CSA_FWD_BN_FUSE=0`` keeps them everywhere (A/B knob)."""
+        on = os.environ.get("CSA_FWD_BN_FUSE", "1") != "0" and not self.forward_only
+        for u in self.units:
+            u.fwd_bn = False
+            if on and u.kind == "dense" and u.xt is not None and u.direct and hasattr(self.lib, "csa_dd_fwd_bn"):
+                u.fwd_bn = self._fwd_bn_ok(u)
+
+    def _fwd_bn_ok(self, u: Unit) -> bool:
+        lp = u.layer
+        return bool(_opt_call(self.lib, "csa_dd_fwd_bn_ok", self.B, lp.spec.hidden, lp.in_shape.numel,
+                              u.in_tf.slab.shape[2]))
+
+    def _fwd_bn_now(self, u: Unit) -> bool:
+        """A planned unit, under the profile flags of the thread that issues this forward."""
+        return bool(getattr(u, "fwd_bn", False)) and self._fwd_bn_ok(u)
+
     def _collect_zero_regions(self) -> None:
         """Accumulators that must start every step at zero.  ``zero_regions`` are cleared
         by the optimizer's zero-list pass; flat-gradient accumulators are cleared by the
@@ -1596,6 +1622,7 @@ class HipProgram:
         img = e.data.images
         V = self.views
         # ---------------- forward ----------------
+        pend = None                      # the carried update's pending flag, when fc1's forward clears it
         if self.pair is not None:
             ua, ub = self.units[0], self.units[1]
             nt = self.units[2].in_tf if len(self.units) > 2 else self.head_tf
@@ -1620,7 +1647,10 @@ class HipProgram:
                 (C.c_void_p * 4)(*[t.data_ptr() for t in fz]), (C.c_long * 4)(*[t.numel() for t in fz]), len(fz),
                 st), "conv_pair_fwd")
             if carrying and self.carry_clear:
-                _opt_call(lib, "csa_ew_clear_next", K.ptr(self.carry_pending))   # (next: bn_act_apply)
+                if self._fwd_bn_now(self.units[2]):
+                    pend = self.carry_pending                                    # (csa_dd_fwd_bn clears it)
+                else:
+                    _opt_call(lib, "csa_ew_clear_next", K.ptr(self.carry_pending))   # (next: bn_act_apply)
             if oslab is not None and self.det:
                 self._row_fold(oslab, nt.prod_rows, oslab.shape[1] * oslab.shape[2], oslab, 0, st)
             if oslab is not None and self.sync_bn:
@@ -1655,6 +1685,14 @@ class HipProgram:
                 fin, fout = lp.in_shape.numel, lp.spec.hidden
                 if u is getattr(self, "br_unit", None):
                     self.join_branch()          # the previous step's update read u.xt and W
+                if u.xt is not None and self._fwd_bn_now(u):
+                    # BatchNorm + activation on load: xt, the tables and the pending flag come
+                    # out of the forward's own launch (dense_direct.hip dd_fwd_wide_bn_kernel)
+                    self._rc(lib.csa_dd_fwd_bn(
+                        K.ptr(u.x), K.ptr(V[f"{lp.name}.weight"]), K.ptr(V[f"{lp.name}.bias"]), K.ptr(u.y),
+                        B, fout, fin, tf.slab.shape[2], *bn, in_act, in_alpha, K.ptr(u.xt),
+                        K.ptr(getattr(tf, "bn_tab", None)), K.ptr(pend if k == 2 else None), st), "dd_fwd_bn")
+                    continue
                 if u.xt is not None:
                     self._rc(lib.csa_bn_act_apply(
                         K.ptr(u.x), K.ptr(u.xt), B * fin, tf.slab.shape[2], *bn, in_act, in_alpha,
