@@ -48,6 +48,7 @@ struct ApsArgs {
   float* s0; float* s1;           // optimizer slots of my shard
   float* selfbox;                 // my own pushes not applied in their launch: [R][sh] (local)
   int opt; float lr;
+  LrSched sched;                  // learning-rate schedule, by apply count (all-zero: constant)
   int* prog;                      // [nb][APS_PROG]: next clock, next source, pushes applied,
                                   //   this rank's clock t, max staleness seen — per workgroup:
                                   //   every launch runs every workgroup once, so the clocks
@@ -145,9 +146,8 @@ __global__ __launch_bounds__(APS_T) void aps_kernel(ApsArgs a) {
     const float* g = s_q != me ? a.inbox[me] + ((long)(s_c % a.R) * W + s_q) * a.sh
                      : (s_c == t && !a.drain ? a.grad + (long)me * a.sh : a.selfbox + (long)(s_c % a.R) * a.sh);
     const int n = s_n + 1;                              // 1-based update count of this chunk
-    const float lr = a.opt == OPT_ADAM
-                         ? a.lr * sqrtf(1.f - powf(0.999f, (float)n)) / (1.f - powf(0.9f, (float)n))
-                         : a.lr;
+    // (the apply count is what TF's global_step is under asynchronous replicas)
+    const float lr = opt_step_lr_at(a.opt, a.lr, (int64_t)n, a.sched);
     // float4 over the chunk (chunk and shard are multiples of 4): one 16-byte load of
     // the uncached inbox per lane instead of four dependent 4-byte round trips
     // four float4s per thread per round, every load of the round issued first (named
@@ -273,9 +273,11 @@ __global__ __launch_bounds__(APS_T) void aps_kernel(ApsArgs a) {
 using namespace csa;
 
 // bufs: per rank {inbox, inflag, outbox, outver, outat} (mapped pointers, rank-major).
-CSA_API int csa_aps_step(int rank, int world, int R, int s, long sh, int nb, void* const* bufs, const float* grad,
-                         float* flat, float* s0, float* s1, float* selfbox, int opt, float lr, int* prog,
-                         unsigned* state, int drain, double timeout_s, hipStream_t st) {
+// (sched: the learning-rate schedule, read here; null = constant)
+CSA_API int csa_aps_step_sched(int rank, int world, int R, int s, long sh, int nb, void* const* bufs,
+                               const float* grad, float* flat, float* s0, float* s1, float* selfbox, int opt, float lr,
+                               int* prog, unsigned* state, int drain, double timeout_s, hipStream_t st,
+                               const LrSched* sched) {
   if (world < 1 || world > APS_MAXR || rank < 0 || rank >= world || R < 2 || s < 0 || sh <= 0 || sh % 4 || nb < 1)
     return -1;
   if (((uintptr_t)grad & 15) || ((uintptr_t)flat & 15) || !selfbox || ((uintptr_t)selfbox & 15)) return -2;
@@ -290,8 +292,16 @@ CSA_API int csa_aps_step(int rank, int world, int R, int s, long sh, int nb, voi
     a.outat[p] = static_cast<int*>(bufs[5 * p + 4]);
   }
   a.grad = grad; a.flat = flat; a.s0 = s0; a.s1 = s1; a.selfbox = selfbox; a.opt = opt; a.lr = lr;
+  a.sched = lr_sched_from(sched);
   a.prog = prog; a.state = state; a.drain = drain;
   a.timeout_ticks = (unsigned long long)(timeout_s * 1.0e8);     // wall_clock64: 100 MHz
   hipLaunchKernelGGL(aps_kernel, dim3((unsigned)nb), dim3(APS_T), 0, st, a);
   return (int)hipGetLastError();
+}
+
+CSA_API int csa_aps_step(int rank, int world, int R, int s, long sh, int nb, void* const* bufs, const float* grad,
+                         float* flat, float* s0, float* s1, float* selfbox, int opt, float lr, int* prog,
+                         unsigned* state, int drain, double timeout_s, hipStream_t st) {
+  return csa_aps_step_sched(rank, world, R, s, sh, nb, bufs, grad, flat, s0, s1, selfbox, opt, lr, prog, state, drain,
+                            timeout_s, st, nullptr);
 }

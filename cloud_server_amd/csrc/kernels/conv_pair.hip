@@ -95,6 +95,7 @@ constexpr int CP_MAXCS = 4;
 struct CPOptCarry {
   int blocks;                          // extra workgroups (0: no carry)
   int opt; float lr; const int64_t* step;
+  LrSched sched;                       // learning-rate schedule (all-zero: constant)
   float* w; const float* g; float* s0; float* s1;
   unsigned* pending;                   // 1: the exchanged gradient awaits its update (cleared
                                        // by the launch after the carrying forward: bn_act_apply)
@@ -121,7 +122,7 @@ __device__ __forceinline__ void cp_opt_carry(const CPOptCarry& c, int k, int nbl
 
 __device__ __forceinline__ void cp_opt_carry_apply(const CPOptCarry& c, int k, int nblk) {
   const int nslot = opt_nslots(c.opt);
-  const float lr = opt_step_lr(c.opt, c.lr, c.step);
+  const float lr = opt_step_lr(c.opt, c.lr, c.step, c.sched);
   const long m4 = c.start4[c.count];
   const long nth = (long)nblk * blockDim.x;
   float4* w4 = reinterpret_cast<float4*>(c.w);
@@ -1253,6 +1254,7 @@ struct CPTail {
                                     // asks for one ticket more than exists (forced timeout);
                                     // the closing tail clears it (one-shot, host-armed)
   int opt; float lr; const int64_t* step;
+  LrSched sched;                    // learning-rate schedule (all-zero: constant)
   const CPTailSeg* segs;            // [param_blocks]
   int nz; float* zp[CP_MAXZ]; int zn[CP_MAXZ];
   // next batch: out_img[b][..] = img[rows[cursor * B + b]][..] (32-bit words), out_lbl
@@ -1290,12 +1292,13 @@ __device__ __forceinline__ bool cp_tail_wait(const CPTail& t, int k, unsigned wa
 // Tail workgroup k < param_blocks: its table entry's 256 elements.  The entry and the
 // parameter / slot values (which no pair workgroup writes) are loaded BEFORE the wait, so
 // after the last pair workgroup only the stripe loads — one round trip — remain.
-struct CPTailPre { CPTailSeg d; float wv, z0, z1; };
+struct CPTailPre { CPTailSeg d; float wv, z0, z1, lrb; };   // lrb: the scheduled base rate
 __device__ __forceinline__ CPTailPre cp_tail_prefetch(const CPTail& t, int k) {
   CPTailPre p;
   p.d = t.segs[k];                                     // uniform address: scalar loads
   const int i = max(min(p.d.base + (int)threadIdx.x, p.d.n - 1), 0);
   const int nslot = opt_nslots(t.opt);
+  p.lrb = opt_sched_lr(t.lr, t.step, t.sched);         // (before the wait: the head advanced the counter)
   p.wv = p.d.w[i];
   p.z0 = nslot >= 1 ? p.d.s0[i] : 0.f;
   p.z1 = nslot >= 2 ? p.d.s1[i] : 0.f;
@@ -1317,7 +1320,7 @@ __device__ __forceinline__ void cp_tail_params(const CPTail& t, int k, CPTailPre
     if (d.store) {
       d.w[i] = gsum;
     } else {
-      opt_update(t.opt, opt_step_lr(t.opt, t.lr, t.step), wv, gsum, z0, z1);
+      opt_update(t.opt, opt_step_lr(t.opt, p.lrb, t.step), wv, gsum, z0, z1);
       d.w[i] = wv;
       if (nslot >= 1) d.s0[i] = z0;
       if (nslot >= 2) d.s1[i] = z1;
@@ -2467,12 +2470,12 @@ static thread_local CPOptCarry g_cp_carry{};
 
 static int cp_carry_make(CPOptCarry& c, int opt, float lr, const int64_t* step, float* w, const float* g, float* s0,
                          float* s1, unsigned* pending, int nseg, const long* seg_lo, const long* seg_hi,
-                         int blocks) {
+                         int blocks, const LrSched* sched) {
   c = CPOptCarry{};
   if (nseg < 1 || nseg > CP_MAXCS || !w || !g || !pending || blocks < 1) return -1;
   if (opt_nslots(opt) >= 1 && !s0) return -1;
   if (opt_nslots(opt) >= 2 && !s1) return -1;
-  c.opt = opt; c.lr = lr; c.step = step; c.w = w; c.g = g; c.s0 = s0; c.s1 = s1; c.pending = pending;
+  c.opt = opt; c.lr = lr; c.step = step; c.sched = lr_sched_from(sched); c.w = w; c.g = g; c.s0 = s0; c.s1 = s1; c.pending = pending;
   c.count = nseg;
   c.start4[0] = 0;
   for (int i = 0; i < nseg; ++i) {
@@ -2484,24 +2487,37 @@ static int cp_carry_make(CPOptCarry& c, int opt, float lr, const int64_t* step, 
   return 0;
 }
 
+// (sched: the update's learning-rate schedule, read here; null = constant)
+CSA_API int csa_conv_pair_fwd_carry_sched(int opt, float lr, const int64_t* step, float* w, const float* g, float* s0,
+                                          float* s1, unsigned* pending, int nseg, const long* seg_lo,
+                                          const long* seg_hi, int blocks, const LrSched* sched) {
+  return cp_carry_make(g_cp_carry, opt, lr, step, w, g, s0, s1, pending, nseg, seg_lo, seg_hi, blocks, sched);
+}
+
 CSA_API int csa_conv_pair_fwd_carry(int opt, float lr, const int64_t* step, float* w, const float* g, float* s0,
                                     float* s1, unsigned* pending, int nseg, const long* seg_lo,
                                     const long* seg_hi, int blocks) {
-  return cp_carry_make(g_cp_carry, opt, lr, step, w, g, s0, s1, pending, nseg, seg_lo, seg_hi, blocks);
+  return csa_conv_pair_fwd_carry_sched(opt, lr, step, w, g, s0, s1, pending, nseg, seg_lo, seg_hi, blocks, nullptr);
 }
 
 // Apply a pending deferred update now (a no-op on the device when none is pending), then
 // clear the flag: every host read of the parameters between steps goes through this.
-CSA_API int csa_opt_carry_flush(int opt, float lr, const int64_t* step, float* w, const float* g, float* s0,
-                                float* s1, unsigned* pending, int nseg, const long* seg_lo, const long* seg_hi,
-                                int blocks, hipStream_t st) {
+CSA_API int csa_opt_carry_flush_sched(int opt, float lr, const int64_t* step, float* w, const float* g, float* s0,
+                                      float* s1, unsigned* pending, int nseg, const long* seg_lo,
+                                      const long* seg_hi, int blocks, hipStream_t st, const LrSched* sched) {
   CPOptCarry c;
-  const int rc = cp_carry_make(c, opt, lr, step, w, g, s0, s1, pending, nseg, seg_lo, seg_hi, blocks);
+  const int rc = cp_carry_make(c, opt, lr, step, w, g, s0, s1, pending, nseg, seg_lo, seg_hi, blocks, sched);
   if (rc) return rc;
   hipLaunchKernelGGL(cp_opt_carry_kernel, dim3((unsigned)blocks), dim3(256), 0, st, c);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return (int)e;
   return (int)hipMemsetAsync(pending, 0, sizeof(unsigned), st);
+}
+
+CSA_API int csa_opt_carry_flush(int opt, float lr, const int64_t* step, float* w, const float* g, float* s0,
+                                float* s1, unsigned* pending, int nseg, const long* seg_lo, const long* seg_hi,
+                                int blocks, hipStream_t st) {
+  return csa_opt_carry_flush_sched(opt, lr, step, w, g, s0, s1, pending, nseg, seg_lo, seg_hi, blocks, st, nullptr);
 }
 
 CSA_API int csa_conv_pair_fwd(const int* geom, const uint8_t* img, const int64_t* idx, const int64_t* cursor,
@@ -2626,13 +2642,16 @@ CSA_API int csa_conv_pair_tail_plan(void* table, int opt, int nseg, float* const
 static thread_local int* g_cp_tail_force = nullptr;
 CSA_API void csa_conv_pair_tail_force(int* force) { g_cp_tail_force = force; }
 
-CSA_API int csa_conv_pair_tail_set(unsigned* tk, int* err, int opt, float lr, const int64_t* step,
-                                   const void* table, int param_blocks, int nz, float* const* zp, const long* zn,
-                                   const uint8_t* img, const int64_t* labels, const int64_t* rows,
-                                   const int64_t* cursor, int B, long imsz, uint8_t* out_img, int64_t* out_lbl) {
+// (sched: the tail update's learning-rate schedule, read here; null = constant)
+CSA_API int csa_conv_pair_tail_set_sched(unsigned* tk, int* err, int opt, float lr, const int64_t* step,
+                                         const void* table, int param_blocks, int nz, float* const* zp,
+                                         const long* zn, const uint8_t* img, const int64_t* labels,
+                                         const int64_t* rows, const int64_t* cursor, int B, long imsz,
+                                         uint8_t* out_img, int64_t* out_lbl, const LrSched* sched) {
   if (!tk || !err || !step || !table || param_blocks < 1 || nz < 0 || nz > CP_MAXZ) return -1;
   CPTail t{};
   t.on = 1; t.tk = tk; t.err = err; t.force = g_cp_tail_force; t.opt = opt; t.lr = lr; t.step = step;
+  t.sched = lr_sched_from(sched);
   t.segs = static_cast<const CPTailSeg*>(table); t.param_blocks = param_blocks;
   t.nz = nz;
   for (int k = 0; k < nz; ++k) { t.zp[k] = zp[k]; t.zn[k] = (int)zn[k]; }
@@ -2646,6 +2665,14 @@ CSA_API int csa_conv_pair_tail_set(unsigned* tk, int* err, int opt, float lr, co
   }
   g_cp_tail = t;
   return 0;
+}
+
+CSA_API int csa_conv_pair_tail_set(unsigned* tk, int* err, int opt, float lr, const int64_t* step,
+                                   const void* table, int param_blocks, int nz, float* const* zp, const long* zn,
+                                   const uint8_t* img, const int64_t* labels, const int64_t* rows,
+                                   const int64_t* cursor, int B, long imsz, uint8_t* out_img, int64_t* out_lbl) {
+  return csa_conv_pair_tail_set_sched(tk, err, opt, lr, step, table, param_blocks, nz, zp, zn, img, labels, rows,
+                                      cursor, B, imsz, out_img, out_lbl, nullptr);
 }
 
 CSA_API int csa_conv_pair_tail_pending() { return g_cp_tail.on; }

@@ -503,6 +503,7 @@ struct DDWgrad {
   float* w; float* b; float* sw0; float* sw1; float* sb0; float* sb1;   // update mode
   int opt; float lr; const int64_t* step;
   int ftiles, ntiles;                           // ntiles: 128-column groups
+  LrSched sched;                                // learning-rate schedule (all-zero: constant)
 };
 
 constexpr int DD_KC = 32;   // MFMA k-steps (x2 batch rows) per register chunk
@@ -537,7 +538,7 @@ __global__ __launch_bounds__(DD_THREADS) void dd_wgrad_kernel(DDWgrad a) {
     if (a.opt < 0) {
       a.db[n] = g;
     } else {
-      const float lr = opt_step_lr(a.opt, a.lr, a.step);
+      const float lr = opt_step_lr(a.opt, a.lr, a.step, a.sched);
       float wv = a.b[n], s0 = a.sb0 ? a.sb0[n] : 0.f, s1 = a.sb1 ? a.sb1[n] : 0.f;
       opt_update(a.opt, lr, wv, g, s0, s1);
       a.b[n] = wv;
@@ -597,7 +598,7 @@ __global__ __launch_bounds__(DD_THREADS) void dd_wgrad_kernel(DDWgrad a) {
     }
     return;
   }
-  const float lr = opt_step_lr(a.opt, a.lr, a.step);
+  const float lr = opt_step_lr(a.opt, a.lr, a.step, a.sched);
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     dd_pin(wv[r]);
@@ -1152,16 +1153,25 @@ CSA_API int csa_dd_dgrad(const float* dY, const float* W, float* dX, int M, int 
 // dW[F][N] = act(X)^T . dY * gscale, db = colsum(dY) * gscale (opt < 0), or the optimizer
 // update of W / b and their slots with that gradient (opt >= 0; step = the device step
 // counter after this step's increment).
-CSA_API int csa_dd_wgrad(const float* X, const float* dY, int M, int F, int N, int act, float alpha, float gscale,
-                         float* dW, float* db, float* W, float* b, float* sW0, float* sW1, float* sb0, float* sb1,
-                         int opt, float lr, const int64_t* step, hipStream_t st) {
+// (sched: the step's learning-rate schedule, read here; null = constant)
+CSA_API int csa_dd_wgrad_sched(const float* X, const float* dY, int M, int F, int N, int act, float alpha,
+                               float gscale, float* dW, float* db, float* W, float* b, float* sW0, float* sW1,
+                               float* sb0, float* sb1, int opt, float lr, const int64_t* step, hipStream_t st,
+                               const LrSched* sched) {
   if (M <= 0 || F <= 0 || N <= 0) return -1;
   if (opt < 0 && (!dW || !db)) return -2;
   if (opt >= 0 && (!W || !b || (opt_nslots(opt) > 0 && (!sW0 || !sb0)) || (opt_nslots(opt) > 1 && (!sW1 || !sb1))))
     return -3;
   DDWgrad a{X, dY, M, F, N, act, alpha, gscale, dW, db, W, b, sW0, sW1, sb0, sb1, opt, lr, step,
-            (F + 31) / 32, (N + 127) / 128};
+            (F + 31) / 32, (N + 127) / 128, lr_sched_from(sched)};
   const int nb = a.ftiles * a.ntiles + (N + 63) / 64;
   hipLaunchKernelGGL(dd_wgrad_kernel, dim3(nb), dim3(DD_THREADS), 0, st, a);
   return (int)hipGetLastError();
+}
+
+CSA_API int csa_dd_wgrad(const float* X, const float* dY, int M, int F, int N, int act, float alpha, float gscale,
+                         float* dW, float* db, float* W, float* b, float* sW0, float* sW1, float* sb0, float* sb1,
+                         int opt, float lr, const int64_t* step, hipStream_t st) {
+  return csa_dd_wgrad_sched(X, dY, M, F, N, act, alpha, gscale, dW, db, W, b, sW0, sW1, sb0, sb1, opt, lr, step, st,
+                            nullptr);
 }

@@ -38,6 +38,7 @@ struct DUArgs {
   float* s0w; float* s1w;   // optimizer slots of W (same [K][N] layout) ...
   float* s0b; float* s1b;   // ... and of the bias
   float scale;
+  LrSched sched;            // learning-rate schedule of the step (all-zero: constant)
   // gradient mode (gW != null, data parallel): the weight / bias GRADIENTS are stored whole
   // into gW / gb (the flat gradient, all-reduced before the optimizer) instead of updating
   float* gW; float* gb;
@@ -174,7 +175,7 @@ __device__ __forceinline__ void du_head_prefetch(const DUArgs& a, int grp, int g
 }
 
 template <int THREADS>
-__device__ __forceinline__ void du_head_finish(const DUArgs& a, DUHead& h, float* s_hw, bool last_block) {
+__device__ __forceinline__ void du_head_finish(const DUArgs& a, DUHead& h, float* s_hw, bool last_block, float lrb) {
   // s_hw: [64][DU_HMAXR] act(hy) | [64][10] dl
   const int t = threadIdx.x, M = a.M;
   float* s_y = s_hw;
@@ -198,7 +199,7 @@ __device__ __forceinline__ void du_head_finish(const DUArgs& a, DUHead& h, float
     if (a.hw) {                                            // in-place update (shared rule)
       const long k = (long)n * DU_HNC + j;
       float w = a.hw[k], z0 = a.hs0w ? a.hs0w[k] : 0.f, z1 = a.hs1w ? a.hs1w[k] : 0.f;
-      opt_update(a.opt, opt_step_lr(a.opt, a.lr, a.step), w, v, z0, z1);
+      opt_update(a.opt, opt_step_lr(a.opt, lrb, a.step), w, v, z0, z1);
       a.hw[k] = w;
       if (a.hs0w) a.hs0w[k] = z0;
       if (a.hs1w) a.hs1w[k] = z1;
@@ -214,7 +215,7 @@ __device__ __forceinline__ void du_head_finish(const DUArgs& a, DUHead& h, float
         for (int m = 0; m < M; ++m) v += s_d[m * DU_HNC + lane];
         if (a.hb) {
           float wb = a.hb[lane], z0 = a.hs0b ? a.hs0b[lane] : 0.f, z1 = a.hs1b ? a.hs1b[lane] : 0.f;
-          opt_update(a.opt, opt_step_lr(a.opt, a.lr, a.step), wb, v, z0, z1);
+          opt_update(a.opt, opt_step_lr(a.opt, lrb, a.step), wb, v, z0, z1);
           a.hb[lane] = wb;
           if (a.hs0b) a.hs0b[lane] = z0;
           if (a.hs1b) a.hs1b[lane] = z1;
@@ -270,6 +271,9 @@ __device__ __forceinline__ void du_body(const DUArgs& a, const int bid, const in
   const bool tabs = a.bn_on && a.bn_tab;
   const int C = a.bn.C > 0 ? a.bn.C : 1;
   constexpr int nslot = NSLOT;
+  // the scheduled base rate (lr_b = lr * m(t); a.lr itself without a schedule), formed here
+  // while nothing is in flight: the rate is completed from it where it always was
+  const float lrb = opt_sched_lr(a.lr, a.step, a.sched);
   DU_STAMP(0);
   float* s_hw;
   if constexpr (UPO) {
@@ -363,7 +367,7 @@ __device__ __forceinline__ void du_body(const DUArgs& a, const int bid, const in
   // (5) head epilogue operands (last dense layer only)
   if (HEAD) du_head_prefetch<THREADS>(a, grp, groups, cb, nb, hd);
 
-  const float lr = opt_step_lr(a.opt, a.lr, a.step);
+  const float lr = opt_step_lr(a.opt, lrb, a.step);
   du_f32x4 dacc[4];
 #pragma unroll
   for (int t = 0; t < 4; ++t) dacc[t] = du_f32x4{0.f, 0.f, 0.f, 0.f};
@@ -510,7 +514,7 @@ __device__ __forceinline__ void du_body(const DUArgs& a, const int bid, const in
     }
   }
   DU_STAMP(3);
-  if (HEAD) du_head_finish<THREADS>(a, hd, s_hw, bid == nblk - 1);
+  if (HEAD) du_head_finish<THREADS>(a, hd, s_hw, bid == nblk - 1, lrb);
   if (!dgrad) {                                            // uniform: first layer
     if (!DGO) du_store_w<NSLOT>(a, wv, s0v, s1v, wofs, sok, i, nf, bown, bn0, bw, bs0, bs1);
     DU_STAMP(6);

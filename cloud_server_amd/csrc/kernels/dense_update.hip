@@ -285,8 +285,9 @@ static DUArgs du_args(const float* dY, float* W, float* bias, float* dX, int M, 
 }
 
 static void du_optimizer(DUArgs& a, int opt, float lr, const int64_t* step, float* s0w, float* s1w, float* s0b,
-                         float* s1b, float scale) {
+                         float* s1b, float scale, const LrSched* sched = nullptr) {
   a.opt = opt; a.lr = lr; a.step = step; a.s0w = s0w; a.s1w = s1w; a.s0b = s0b; a.s1b = s1b; a.scale = scale;
+  a.sched = lr_sched_from(sched);
 }
 
 // The head epilogue's arguments (see DUArgs); false when hy is given and another one is missing.
@@ -334,6 +335,22 @@ static int du_run(const DUArgs& a, bool head_ok, hipStream_t st) {
 
 // ... plus the head epilogue (hy != null): dWh / dbh of the row-per-workgroup head and the
 // step's metric ring entry are reduced by this launch (see DUArgs).
+// (sched: the step's learning-rate schedule, read here; null = constant)
+CSA_API int csa_dense_bwd_update_head_sched(const float* dY, float* W, float* bias, float* dX, int M, int K, int N,
+                                      const float* x_fwd, int act, float alpha, const float* bn_slab, int bn_nslab,
+                                      int bn_C, float bn_count, float bn_eps, const float* bn_scale,
+                                      const float* bn_offset, float* bwd_slab, const float* Xw, int opt, float lr,
+                                      const int64_t* step, float* s0w, float* s1w, float* s0b, float* s1b,
+                                      float scale, const float* bn_tab, float* part, unsigned* cnt,
+                                      const float* hy, const float* hdl, float* hgw, float* hgb, const float* hrl,
+                                      const int* hrc, float* ring_loss, int* ring_correct, int ring, float ldiv,
+                                      int hact, float halpha, hipStream_t st, const LrSched* sched) {
+  DUArgs a = du_args(dY, W, bias, dX, M, K, N, x_fwd, act, alpha, bn_slab, bn_nslab, bn_C, bn_count, bn_eps,
+                     bn_scale, bn_offset, bwd_slab, Xw, bn_tab, part, cnt);
+  du_optimizer(a, opt, lr, step, s0w, s1w, s0b, s1b, scale, sched);
+  return du_run(a, du_head(a, hy, hdl, hgw, hgb, hrl, hrc, ring_loss, ring_correct, ring, ldiv, hact, halpha), st);
+}
+
 CSA_API int csa_dense_bwd_update_head(const float* dY, float* W, float* bias, float* dX, int M, int K, int N,
                                       const float* x_fwd, int act, float alpha, const float* bn_slab, int bn_nslab,
                                       int bn_C, float bn_count, float bn_eps, const float* bn_scale,
@@ -343,10 +360,10 @@ CSA_API int csa_dense_bwd_update_head(const float* dY, float* W, float* bias, fl
                                       const float* hy, const float* hdl, float* hgw, float* hgb, const float* hrl,
                                       const int* hrc, float* ring_loss, int* ring_correct, int ring, float ldiv,
                                       int hact, float halpha, hipStream_t st) {
-  DUArgs a = du_args(dY, W, bias, dX, M, K, N, x_fwd, act, alpha, bn_slab, bn_nslab, bn_C, bn_count, bn_eps,
-                     bn_scale, bn_offset, bwd_slab, Xw, bn_tab, part, cnt);
-  du_optimizer(a, opt, lr, step, s0w, s1w, s0b, s1b, scale);
-  return du_run(a, du_head(a, hy, hdl, hgw, hgb, hrl, hrc, ring_loss, ring_correct, ring, ldiv, hact, halpha), st);
+  return csa_dense_bwd_update_head_sched(dY, W, bias, dX, M, K, N, x_fwd, act, alpha, bn_slab, bn_nslab, bn_C,
+                                         bn_count, bn_eps, bn_scale, bn_offset, bwd_slab, Xw, opt, lr, step, s0w, s1w,
+                                         s0b, s1b, scale, bn_tab, part, cnt, hy, hdl, hgw, hgb, hrl, hrc, ring_loss,
+                                         ring_correct, ring, ldiv, hact, halpha, st, nullptr);
 }
 
 CSA_API int csa_dense_bwd_update(const float* dY, float* W, float* bias, float* dX, int M, int K, int N,
@@ -424,16 +441,17 @@ CSA_API int csa_dense_bwd_dgrad(const float* dY, const float* W, float* dX, int 
 // workgroups of 256 threads.  hy != null: the head epilogue rides along (dWh / dbh into the
 // flat gradient, the step's metric ring entry; see DUArgs).  Returns the segment count, or
 // < 0 when the shape is outside the family or the list is full.
-CSA_API int csa_dense_update_defer(const float* dY, float* W, float* bias, int M, int K, int N, const float* Xw,
+CSA_API int csa_dense_update_defer_sched(const float* dY, float* W, float* bias, int M, int K, int N, const float* Xw,
                                    int opt, float lr, const int64_t* step, float* s0w, float* s1w, float* s0b,
                                    float* s1b, float scale, const float* hy, const float* hdl, float* hgw,
                                    float* hgb, const float* hrl, const int* hrc, float* ring_loss,
-                                   int* ring_correct, int ring, float ldiv, int hact, float halpha) {
+                                   int* ring_correct, int ring, float ldiv, int hact, float halpha,
+                                         const LrSched* sched) {
   if (!csa_dense_bwd_update_ok(M, K, N, 0) || N % 128 || !Xw || !W || !dY || !step) return -1;
   if (g_du_def.n >= DU_MAXDEF) return -3;
   DUArgs a = du_args(dY, W, bias, nullptr, M, K, N, nullptr, 0, 0.f, nullptr, 0, 1, 1.f, 0.f, nullptr, nullptr,
                      nullptr, Xw, nullptr, nullptr, nullptr);
-  du_optimizer(a, opt, lr, step, s0w, s1w, s0b, s1b, scale);
+  du_optimizer(a, opt, lr, step, s0w, s1w, s0b, s1b, scale, sched);
   a.cs = N / 128;
   if (!du_head(a, hy, hdl, hgw, hgb, hrl, hrc, ring_loss, ring_correct, ring, ldiv, hact, halpha) ||
       (hy && g_du_def.head >= 0))
@@ -444,6 +462,15 @@ CSA_API int csa_dense_update_defer(const float* dY, float* W, float* bias, int M
   g_du_def.blocks[g_du_def.n] = ((K + DU_FT - 1) / DU_FT) * a.cs;
   g_du_def.seg[g_du_def.n++] = a;
   return g_du_def.n;
+}
+
+CSA_API int csa_dense_update_defer(const float* dY, float* W, float* bias, int M, int K, int N, const float* Xw,
+                                   int opt, float lr, const int64_t* step, float* s0w, float* s1w, float* s0b,
+                                   float* s1b, float scale, const float* hy, const float* hdl, float* hgw,
+                                   float* hgb, const float* hrl, const int* hrc, float* ring_loss,
+                                   int* ring_correct, int ring, float ldiv, int hact, float halpha) {
+  return csa_dense_update_defer_sched(dY, W, bias, M, K, N, Xw, opt, lr, step, s0w, s1w, s0b, s1b, scale, hy, hdl, hgw,
+                                      hgb, hrl, hrc, ring_loss, ring_correct, ring, ldiv, hact, halpha, nullptr);
 }
 
 CSA_API int csa_dense_update_pending() { return g_du_def.n; }

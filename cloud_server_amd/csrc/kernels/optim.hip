@@ -79,6 +79,7 @@ struct OptArgs {
   float* gz;                       // if set (== g): each thread zeroes the gradient it read
   KeepList keep;                   // ... except inside these ranges (float4-aligned)
   float lr; const int64_t* step;   // 1-based step (the head kernel already advanced it)
+  LrSched sched;                   // learning-rate schedule of the step (all-zero: constant)
   ZeroList z; FoldList fold; MetricFold met;
   int64_t* cursor;                 // batch-stream cursor: += 1 (mod cursor_wrap) per step
   long cursor_wrap;
@@ -189,7 +190,7 @@ __global__ __launch_bounds__(256) void optim_kernel(OptArgs a) {
   }
   const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const long nth = (long)nmain * blockDim.x;
-  const float lr = opt_step_lr(a.opt, a.lr, a.step);
+  const float lr = opt_step_lr(a.opt, a.lr, a.step, a.sched);
   const long n4 = a.seg.start4[a.seg.count];
   float4* w4 = (float4*)a.w;
   const float4* g4 = (const float4*)a.g;
@@ -272,7 +273,7 @@ __global__ __launch_bounds__(256) void optim_fast_kernel(OptArgs a) {
   }
   const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const long nth = (long)nmain * blockDim.x;
-  const float lr = opt_step_lr(a.opt, a.lr, a.step);
+  const float lr = opt_step_lr(a.opt, a.lr, a.step, a.sched);
   float4* w4 = (float4*)a.w;
   const float4* g4 = (const float4*)a.g;
   float4* s04 = (float4*)a.s0;
@@ -414,7 +415,8 @@ CSA_API int csa_optimizer2(int opt, float* w, float* g, float* s0, float* s1, lo
 
 // ... plus the next step's batch staging (st_out_img != null; the head advanced the
 // cursor, so pass cursor = null here).
-CSA_API int csa_optimizer2s(int opt, float* w, float* g, float* s0, float* s1, long n, const long* seg_lo,
+// (sched: the step's learning-rate schedule, read here; null = constant)
+CSA_API int csa_optimizer2s_sched(int opt, float* w, float* g, float* s0, float* s1, long n, const long* seg_lo,
                             const long* seg_hi, int nseg, int zero_grad, float lr, const int64_t* step,
                             float* const* zero_ptrs, const long* zero_ns, int nzero, const long* fold_off,
                             const long* fold_n, float* const* fold_src, const int* fold_S, const long* fold_ld,
@@ -423,7 +425,7 @@ CSA_API int csa_optimizer2s(int opt, float* w, float* g, float* s0, float* s1, l
                             float* ring_loss, int* ring_correct, int ring, int64_t* cursor, long cursor_wrap,
                             const uint8_t* st_img, const int64_t* st_labels, const int64_t* st_rows,
                             const int64_t* st_cursor, int st_B, long st_imsz, uint8_t* st_out_img,
-                            int64_t* st_out_lbl, hipStream_t st) {
+                            int64_t* st_out_lbl, hipStream_t st, const LrSched* sched) {
   if (st_out_img && (st_imsz % 4 || st_B <= 0)) return -1;
   if (n % 4 || nzero > MAXZ || nfold > MAXF || nkeep > MAXK || nseg > MAXSEG) return -1;
   OptArgs a{};
@@ -446,6 +448,7 @@ CSA_API int csa_optimizer2s(int opt, float* w, float* g, float* s0, float* s1, l
   a.cursor = cursor;
   a.cursor_wrap = cursor_wrap;
   a.opt = opt; a.w = w; a.g = g; a.s0 = s0; a.s1 = s1; a.lr = lr; a.step = step;
+  a.sched = lr_sched_from(sched);
   a.gz = zero_grad ? g : nullptr;
   a.z.count = nzero;
   for (int i = 0; i < nzero; ++i) { a.z.p[i] = zero_ptrs[i]; a.z.n[i] = zero_ns[i]; }
@@ -508,6 +511,23 @@ CSA_API int csa_optimizer2s(int opt, float* w, float* g, float* s0, float* s1, l
   return (int)hipGetLastError();
 }
 
+CSA_API int csa_optimizer2s(int opt, float* w, float* g, float* s0, float* s1, long n, const long* seg_lo,
+                            const long* seg_hi, int nseg, int zero_grad, float lr, const int64_t* step,
+                            float* const* zero_ptrs, const long* zero_ns, int nzero, const long* fold_off,
+                            const long* fold_n, float* const* fold_src, const int* fold_S, const long* fold_ld,
+                            const int* fold_zero, int nfold, const long* keep_lo, const long* keep_hi, int nkeep,
+                            const float* met_loss, const int* met_corr, int met_parts, float met_div,
+                            float* ring_loss, int* ring_correct, int ring, int64_t* cursor, long cursor_wrap,
+                            const uint8_t* st_img, const int64_t* st_labels, const int64_t* st_rows,
+                            const int64_t* st_cursor, int st_B, long st_imsz, uint8_t* st_out_img,
+                            int64_t* st_out_lbl, hipStream_t st) {
+  return csa_optimizer2s_sched(opt, w, g, s0, s1, n, seg_lo, seg_hi, nseg, zero_grad, lr, step, zero_ptrs, zero_ns,
+                               nzero, fold_off, fold_n, fold_src, fold_S, fold_ld, fold_zero, nfold, keep_lo, keep_hi,
+                               nkeep, met_loss, met_corr, met_parts, met_div, ring_loss, ring_correct, ring, cursor,
+                               cursor_wrap, st_img, st_labels, st_rows, st_cursor, st_B, st_imsz, st_out_img,
+                               st_out_lbl, st, nullptr);
+}
+
 // Backward-compatible entry: the whole buffer, the head wrote the metric ring itself.
 CSA_API int csa_optimizer(int opt, float* w, float* g, float* s0, float* s1, long n, int zero_grad,
                           float lr, const int64_t* step, float* const* zero_ptrs, const long* zero_ns,
@@ -533,5 +553,24 @@ CSA_API int csa_zero(float* const* ptrs, const long* ns, int count, hipStream_t 
   z.count = count;
   for (int i = 0; i < count; ++i) { z.p[i] = ptrs[i]; z.n[i] = ns[i]; }
   hipLaunchKernelGGL(zero_kernel, dim3(256), dim3(256), 0, st, z);
+  return (int)hipGetLastError();
+}
+
+// Tests only: out[i] = opt_step_lr at the 1-based step steps[i] (no counter is read).
+// sched == null evaluates the schedule-free overload, so a test can hold the constant
+// schedule to it bitwise.
+__global__ __launch_bounds__(256) void lr_sched_eval_kernel(int opt, float lr, LrSched s, int legacy,
+                                                            const int64_t* steps, int n, float* out) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  out[i] = legacy ? opt_step_lr(opt, lr, steps + i) : opt_step_lr(opt, lr, steps + i, s);
+}
+
+CSA_API int csa_lr_sched_eval(int opt, float lr, const LrSched* sched, const int64_t* steps, int n, float* out,
+                              hipStream_t st) {
+  if (n < 1 || !steps || !out) return -1;
+  if (sched && sched->kind != LR_CONSTANT && sched->decay_steps < 1) return -2;
+  hipLaunchKernelGGL(lr_sched_eval_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, opt, lr,
+                     lr_sched_from(sched), sched ? 0 : 1, steps, n, out);
   return (int)hipGetLastError();
 }

@@ -17,6 +17,9 @@ Reference quirks and how they are handled:
 * ``isBias`` is a string compare against ``"False"`` (construct_distribute.py:228): kept.
 * unknown layer names are skipped silently in the reference; we keep them in the parsed
   config (so ``model.json`` round-trips) but they produce no layer.
+* the step size never changes in the reference (one ``AdagradOptimizer(1e-4)``):
+  ``options.lr_schedule`` adds decay and warm-up as a pure function of the step counter
+  (ops/lr_schedule.py); a config without it trains at the constant rate, as before.
 * ``keep_prob`` fed but never used (construct_distribute.py:364-417 feeds 0.5 / 1.0; the
   ``tf.nn.dropout`` line is a comment, construct_distribute_url.py:328): a ``dropout``
   layer is a real layer here; a config without one trains without dropout, as before.
@@ -37,6 +40,7 @@ OPTIMIZERS = ("GradientDescentOptimizer", "AdagradOptimizer", "AdamOptimizer", "
 ACTIVATIONS = ("sigmoid", "relu", "leaky_relu")
 INITS = ("norm", "zero", "xavier")
 PADDINGS = ("SAME", "VALID")
+LR_SCHEDULES = ("constant", "exponential", "inverse_time", "cosine")
 
 
 class ConfigError(ValueError):
@@ -303,6 +307,74 @@ def plan_network(layers: Sequence[LayerSpec], in_hw: int = INPUT_HW, in_c: int =
     return NetPlan(plans, shape.numel, num_classes)
 
 
+@dataclass(frozen=True)
+class LrSchedule:
+    """``options.lr_schedule``: the step's rate as a function of the step counter
+    (ops/lr_schedule.py is the definition of the arithmetic)."""
+    type: str = "constant"
+    decay_steps: int = 1                   # S
+    decay_rate: float = 1.0                # r
+    staircase: bool = False                # floor the step ratio (exponential, inverse_time)
+    alpha: float = 0.0                     # cosine: floor, as a fraction of the base rate
+    warmup_steps: int = 0                  # W: linear warm-up on top of any type
+
+
+_LR_SCHEDULE_KEYS = ("type", "decay_steps", "decay_rate", "staircase", "alpha", "warmup_steps")
+
+
+def _as_bool(v: Any, name: str) -> bool:
+    if isinstance(v, bool):
+        return v
+    if isinstance(v, (int, float)) and v in (0, 1):
+        return bool(v)
+    if isinstance(v, str) and v.strip().lower() in ("true", "false", "1", "0", "yes", "no"):
+        return v.strip().lower() in ("true", "1", "yes")
+    raise ConfigError(f"{name}: expected bool, got {v!r}")
+
+
+def _as_whole(v: Any, name: str) -> int:
+    """An int, or a string / float that holds one (``"3"``, ``3.0``): never a truncation."""
+    if isinstance(v, bool):
+        raise ConfigError(f"{name}: expected int, got {v!r}")
+    f = _as_float(v, name)
+    if not math.isfinite(f) or f != int(f):
+        raise ConfigError(f"{name}: expected int, got {v!r}")
+    return int(f)
+
+
+def parse_lr_schedule(d: Any) -> LrSchedule:
+    """``options.lr_schedule`` -> LrSchedule (numbers may be strings)."""
+    where = "options.lr_schedule"
+    if not isinstance(d, dict):
+        raise ConfigError(f"{where} must be an object")
+    unknown = sorted(set(d) - set(_LR_SCHEDULE_KEYS))
+    if unknown:
+        raise ConfigError(f"{where}: unknown key(s) {unknown}; valid: {list(_LR_SCHEDULE_KEYS)}")
+    kind = d.get("type", "constant")
+    if kind not in LR_SCHEDULES:
+        raise ConfigError(f"{where}.type must be one of {LR_SCHEDULES}")
+    S, r = 1, 1.0
+    if kind != "constant" or "decay_steps" in d:
+        if "decay_steps" not in d:
+            raise ConfigError(f"{where}: {kind} needs decay_steps")
+        S = _as_whole(d["decay_steps"], where + ".decay_steps")
+        if not (1 <= S < 2 ** 31):
+            raise ConfigError(f"{where}.decay_steps must be >= 1")
+    if kind in ("exponential", "inverse_time") or "decay_rate" in d:
+        if "decay_rate" not in d:
+            raise ConfigError(f"{where}: {kind} needs decay_rate")
+        r = _as_float(d["decay_rate"], where + ".decay_rate")
+        if not math.isfinite(r) or r < 0 or (kind == "exponential" and not (0.0 < r <= 1.0)):
+            raise ConfigError(f"{where}.decay_rate must be in (0, 1] for exponential, >= 0 for inverse_time")
+    alpha = _as_float(d.get("alpha", 0.0), where + ".alpha")
+    if not (0.0 <= alpha <= 1.0):
+        raise ConfigError(f"{where}.alpha must be in [0, 1]")
+    W = _as_whole(d.get("warmup_steps", 0), where + ".warmup_steps")
+    if not (0 <= W < 2 ** 31):
+        raise ConfigError(f"{where}.warmup_steps must be >= 0")
+    return LrSchedule(kind, S, r, _as_bool(d.get("staircase", False), where + ".staircase"), alpha, W)
+
+
 @dataclass
 class TrainConfig:
     """The whole ``model.json`` (API.md:306-332) in typed form."""
@@ -325,6 +397,7 @@ class TrainConfig:
     seed: int = 0
     eval_every: int = 0                    # held-out validation sweep every k steps (0 = off)
     eval_batch: int = 256                  # rows per validation batch
+    lr_schedule: LrSchedule = LrSchedule()  # decay / warm-up of the rate by the step counter
 
     @property
     def effective_optimizer(self) -> str:
@@ -383,7 +456,11 @@ def parse_train_config(cfg: Union[str, bytes, Dict[str, Any]]) -> TrainConfig:
         seed=_as_int(ext.get("seed", 0), "seed"),
         eval_every=_as_int(ext.get("eval_every", 0), "eval_every"),
         eval_batch=_as_int(ext.get("eval_batch", 256), "eval_batch"),
+        lr_schedule=parse_lr_schedule(ext["lr_schedule"]) if "lr_schedule" in ext else LrSchedule(),
     )
+    if tc.compat_adagrad and tc.lr_schedule.type != "constant":
+        # the flag means "the reference's fixed Adagrad 1e-4"
+        raise ConfigError("options.lr_schedule: compat_adagrad fixes the rate (only type 'constant' goes with it)")
     if tc.eval_every < 0:
         raise ConfigError("eval_every must be >= 0")
     if tc.eval_batch <= 0:

@@ -193,6 +193,16 @@ _SIGS = {
     "csa_aps_step": (I, [I, I, I, I, L, I, P, P, P, P, P, P, I, F, P, P, I, C.c_double, P]),
 }
 
+# Learning-rate schedules (ops/lr_schedule.py): every launcher that forms the step's rate
+# has a sibling ``<name>_sched`` with one more, LAST argument: a ``const LrSched*`` read on
+# the host (null: the constant rate — what the plain name passes).
+_SCHED_SIBLINGS = ("csa_optimizer2s", "csa_dense_bwd_update_head", "csa_dense_update_defer", "csa_dd_wgrad",
+                   "csa_conv_pair_fwd_carry", "csa_opt_carry_flush", "csa_conv_pair_tail_set", "csa_aps_step")
+for _n in _SCHED_SIBLINGS:
+    _SIGS[_n + "_sched"] = (_SIGS[_n][0], _SIGS[_n][1] + [P])
+# tests only: opt_step_lr at n given 1-based steps (opt, lr, sched, steps, n, out, stream)
+_SIGS["csa_lr_sched_eval"] = (I, [I, F, P, P, I, P, P])
+
 
 def lib_path() -> str:
     """The in-tree kernel library (``CSA_KERNEL_LIB`` overrides it: A/B runs of a kernel
@@ -235,6 +245,14 @@ def load(required: bool = True) -> Optional[C.CDLL]:
         fn.argtypes = args
     _LIB = lib
     return lib
+
+
+def sched_call(lib, name: str, sched, *args):
+    """``name(*args)`` at the constant rate (``sched`` None: the very call made before
+    schedules existed), else its ``_sched`` sibling with the ``LrSchedC`` by pointer."""
+    if sched is None:
+        return getattr(lib, name)(*args)
+    return getattr(lib, name + "_sched")(*args, C.byref(sched))
 
 
 def ptr(t: Optional[torch.Tensor]) -> Optional[int]:

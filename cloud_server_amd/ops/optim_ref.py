@@ -64,3 +64,24 @@ def step_ref(opt_id: int, w: torch.Tensor, g: torch.Tensor, slots: torch.Tensor,
         w.add_(upd, alpha=-lr)
     else:
         raise ValueError(opt_id)
+
+
+@torch.no_grad()
+def step_ref_t(opt_id: int, w: torch.Tensor, g: torch.Tensor, slots: torch.Tensor, lr: torch.Tensor) -> None:
+    """``step_ref`` for the three rules without a bias correction, with the step's rate as a
+    device tensor (a scheduled rate, ops/lr_schedule.py: no host read, so the eager program
+    still captures into a graph).  Adam forms its own rate tensor (``adam_lr_tensor``)."""
+    if opt_id == OPT_SGD:
+        w.sub_(lr * g)
+    elif opt_id == OPT_ADAGRAD:
+        acc = slots[0]
+        acc.addcmul_(g, g)
+        w.sub_(lr * g / acc.sqrt())
+    elif opt_id == OPT_ADADELTA:
+        acc, acc_up = slots[0], slots[1]
+        acc.mul_(ADADELTA_RHO).addcmul_(g, g, value=1 - ADADELTA_RHO)
+        upd = (acc_up + ADADELTA_EPS).sqrt().div_((acc + ADADELTA_EPS).sqrt()).mul_(g)
+        acc_up.mul_(ADADELTA_RHO).addcmul_(upd, upd, value=1 - ADADELTA_RHO)
+        w.sub_(lr * upd)
+    else:
+        raise ValueError(opt_id)

@@ -46,7 +46,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 import torch.distributed as dist
 
-from ..ops import optim_ref
+from ..ops import lr_schedule, optim_ref
 from .xgmi import _line_up, max_blocks_from_env, pool_get, pool_put
 
 GRAD, PARAM = 0, 1
@@ -68,9 +68,13 @@ def _tag(kind: int, clock: int) -> int:
 class AsyncPSGloo:
     """The protocol over torch.distributed isend / irecv (CPU tensors, gloo)."""
 
-    def __init__(self, rank: int, world: int, shard: int, staleness: int, opt_id: int, lr: float):
+    def __init__(self, rank: int, world: int, shard: int, staleness: int, opt_id: int, lr: float, sched=None):
         self.r, self.W, self.sh, self.s = rank, world, shard, staleness
         self.opt_id, self.lr = opt_id, lr
+        # the learning-rate schedule runs on the apply count (TF's global_step under
+        # asynchronous replicas); None: the constant rate
+        self.sched = sched
+        self.lr_used: List[float] = []            # scheduled runs: the rate of every apply, in order
         self.next_apply = (0, 0)                  # (clock, source) of the next push to apply
         self.applied = 0                          # pushes applied (Adam's 1-based t)
         self.grad_recv: Dict[Tuple[int, int], Tuple[object, torch.Tensor]] = {}
@@ -101,7 +105,12 @@ class AsyncPSGloo:
 
     def _apply(self, w: torch.Tensor, slots: torch.Tensor, g: torch.Tensor) -> None:
         self.applied += 1
-        optim_ref.step_ref(self.opt_id, w, g, slots, self.lr, self.applied)
+        if self.sched is None:
+            optim_ref.step_ref(self.opt_id, w, g, slots, self.lr, self.applied)
+            return
+        lr = float(lr_schedule.lr_f32(self.sched, self.lr, self.applied))
+        self.lr_used.append(lr)
+        optim_ref.step_ref(self.opt_id, w, g, slots, lr, self.applied)
 
     def applied_through(self) -> int:
         c, q = self.next_apply
@@ -192,8 +201,10 @@ class AsyncPSDevice:
     (csrc/comm/async_ps.hip), capturable in the step's HIP graph."""
 
     def __init__(self, rank: int, world: int, shard: int, staleness: int, opt_id: int, lr: float,
-                 device: torch.device, group=None, timeout_s: Optional[float] = None):
+                 device: torch.device, group=None, timeout_s: Optional[float] = None, sched=None):
         from ..ops import fused as K
+        self._K = K
+        self.sched_c = lr_schedule.to_c(sched)     # by the chunk's apply count (None: constant)
         if shard % 4:
             raise ValueError("async_ps: the shard must be a multiple of 4 floats")
         self.lib = K.load(required=True)
@@ -276,7 +287,8 @@ class AsyncPSDevice:
     def _launch(self, flat_grad, flat, slots, drain: int) -> None:
         s0 = slots[0, :] if slots.shape[0] > 0 else None
         s1 = slots[1, :] if slots.shape[0] > 1 else None
-        rc = self.lib.csa_aps_step(
+        rc = self._K.sched_call(
+            self.lib, "csa_aps_step", self.sched_c,
             self.r, self.W, self.R, self.s, self.sh, self.nb, self._bufs, flat_grad.data_ptr(), flat.data_ptr(),
             None if s0 is None else s0.data_ptr(), None if s1 is None else s1.data_ptr(),
             self.selfbox.data_ptr(), self.opt_id,
@@ -333,5 +345,5 @@ def make_async_ps(eng, lo: int, hi: int):
     s = staleness_from(eng.cfg)
     ctx = eng.ctx
     if eng.device.type == "cuda":
-        return AsyncPSDevice(ctx.rank, ctx.world, hi - lo, s, eng.opt_id, eng.lr, eng.device)
-    return AsyncPSGloo(ctx.rank, ctx.world, hi - lo, s, eng.opt_id, eng.lr)
+        return AsyncPSDevice(ctx.rank, ctx.world, hi - lo, s, eng.opt_id, eng.lr, eng.device, sched=eng.lr_sched)
+    return AsyncPSGloo(ctx.rank, ctx.world, hi - lo, s, eng.opt_id, eng.lr, sched=eng.lr_sched)

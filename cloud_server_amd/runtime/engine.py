@@ -29,7 +29,7 @@ from ..data.datasets import ArrayDataset
 from ..data.stream import BatchStream, DeviceDataset
 from ..models.cnn import DigitNet, build_model, loss_fn
 from ..models.dsl import TrainConfig
-from ..ops import optim_ref
+from ..ops import lr_schedule, optim_ref
 from ..parallel.dist import DistContext, ranks_share_gpu
 from ..parallel.dp import GradSync
 from ..utils.tracing import trace_range
@@ -115,6 +115,10 @@ class TrainEngine:
         self.sync.broadcast_params(self.flat)
         self.opt_id = optim_ref.OPT_IDS[cfg.effective_optimizer]
         self.lr = cfg.effective_lr
+        # the parsed schedule beside the base rate (None: the constant rate — every path then
+        # runs the code it ran before schedules existed); the device's by-value argument
+        self.lr_sched = cfg.lr_schedule if lr_schedule.active(cfg.lr_schedule) else None
+        self.lr_sched_c = lr_schedule.to_c(self.lr_sched)
         lo, hi = self.sync.shard_range()
         self.slots = optim_ref.init_slots(self.opt_id, hi - lo, self.device)
         self.grad_shard = torch.zeros(hi - lo, device=self.device) if strategy == "ps" else None
@@ -180,9 +184,14 @@ class TrainEngine:
         self.warmed = False      # _warm_up ran (a packed host re-captures without it)
 
     # ---------------- pieces used by the programs (device ops only) ----------------
+    def lr_tensor(self) -> torch.Tensor:
+        """The scheduled rate of the step being computed, on the device (no host read)."""
+        return lr_schedule.lr_torch(self.lr_sched, self.lr, self.dstep + 1)
+
     def adam_lr_tensor(self) -> torch.Tensor:
         t = (self.dstep + 1).to(torch.float32)
-        return self.lr * torch.sqrt(1 - optim_ref.ADAM_B2 ** t) / (1 - optim_ref.ADAM_B1 ** t)
+        lr = self.lr if self.lr_sched is None else self.lr_tensor()
+        return lr * torch.sqrt(1 - optim_ref.ADAM_B2 ** t) / (1 - optim_ref.ADAM_B1 ** t)
 
     def apply_update(self) -> None:
         """Grad sync + optimizer on the flat buffers (torch ops; the HIP program fuses this)."""
@@ -213,6 +222,8 @@ class TrainEngine:
             m.mul_(optim_ref.ADAM_B1).add_(g, alpha=1 - optim_ref.ADAM_B1)
             v.mul_(optim_ref.ADAM_B2).addcmul_(g, g, value=1 - optim_ref.ADAM_B2)
             w.sub_(self.adam_lr_tensor() * m / (v.sqrt() + optim_ref.ADAM_EPS))
+        elif self.lr_sched is not None:
+            optim_ref.step_ref_t(self.opt_id, w, g, slots, self.lr_tensor())
         else:
             optim_ref.step_ref(self.opt_id, w, g, slots, self.lr, 1)
 

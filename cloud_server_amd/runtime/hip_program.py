@@ -332,8 +332,8 @@ class HipProgram:
         when none is pending) and clear its flag."""
         if getattr(self, "carry", None) is None:
             return
-        self._rc(self.lib.csa_opt_carry_flush(*self._carry_args(), st if st is not None else K.stream()),
-                 "opt_carry_flush")
+        self._rc(K.sched_call(self.lib, "csa_opt_carry_flush", self.e.lr_sched_c, *self._carry_args(),
+                              st if st is not None else K.stream()), "opt_carry_flush")
 
     # ------------------------------------------------------------------ DP overlap
     def _plan_grad_buckets(self) -> None:
@@ -827,7 +827,8 @@ class HipProgram:
         hw, hb, hs0w, hs1w, hs0b, hs1b = self.head_params
         self._rc(lib.csa_dense_update_head_params(K.ptr(hw), K.ptr(hb), K.ptr(hs0w), K.ptr(hs1w), K.ptr(hs0b),
                                                   K.ptr(hs1b)), "dense_update_head_params")
-        rc = lib.csa_conv_pair_tail_set(
+        rc = K.sched_call(
+            lib, "csa_conv_pair_tail_set", e.lr_sched_c,
             K.ptr(self.tail_tk), K.ptr(self.tail_err), e.opt_id, float(e.lr), K.ptr(e.dstep),
             K.ptr(self.tail_table), self.tail_blocks,
             len(self.tail_zero), (P * 4)(*[t.data_ptr() for t in self.tail_zero]),
@@ -1633,7 +1634,8 @@ class HipProgram:
             fz = [] if getattr(self, "_predicting", False) else getattr(self, "fwd_zero", [])
             carrying = getattr(self, "carry", None) is not None and not getattr(self, "_predicting", False)
             if carrying:
-                self._rc(lib.csa_conv_pair_fwd_carry(*self._carry_args()), "conv_pair_fwd_carry")
+                self._rc(K.sched_call(lib, "csa_conv_pair_fwd_carry", e.lr_sched_c, *self._carry_args()),
+                         "conv_pair_fwd_carry")
             c1 = None if getattr(self, "_predicting", False) else getattr(self, "pair_c1", None)
             if c1 is not None:
                 _opt_call(lib, "csa_conv_pair_c1_fwd", K.ptr(c1), c1.numel())
@@ -1998,7 +2000,8 @@ class HipProgram:
         s0 = sl[0] if sl.shape[0] > 0 else None
         s1 = sl[1] if sl.shape[0] > 1 else None
         V = self.views
-        self._rc(self.lib.csa_dd_wgrad(
+        self._rc(K.sched_call(
+            self.lib, "csa_dd_wgrad", e.lr_sched_c,
             K.ptr(x), K.ptr(dy), M, fin, fout, act[0], act[1], 1.0, None, None,
             K.ptr(V[f"{lp.name}.weight"]), K.ptr(V[f"{lp.name}.bias"]),
             K.ptr(s0[ow:]) if s0 is not None else None, K.ptr(s1[ow:]) if s1 is not None else None,
@@ -2038,7 +2041,8 @@ class HipProgram:
                 if rc >= 0:
                     rc = lib.csa_dense_update_grad_mode(K.ptr(G[f"{lp.name}.weight"]), K.ptr(G[f"{lp.name}.bias"]))
             else:
-                rc = lib.csa_dense_update_defer(
+                rc = K.sched_call(
+                    lib, "csa_dense_update_defer", e.lr_sched_c,
                     K.ptr(u.dy), K.ptr(self.views[f"{lp.name}.weight"]), K.ptr(self.views[f"{lp.name}.bias"]),
                     B, fin, fout, K.ptr(xw), e.opt_id, float(e.lr), K.ptr(e.dstep),
                     K.ptr(s0[ow:]) if s0 is not None else None, K.ptr(s1[ow:]) if s1 is not None else None,
@@ -2072,7 +2076,8 @@ class HipProgram:
                 self._row_fold(tf.bwd_slab, tf.bwd_prod_rows, tf.bwd_slab.shape[1] * tf.bwd_slab.shape[2],
                                tf.bwd_slab, 0, st)
             return
-        self._rc(lib.csa_dense_bwd_update_head(
+        self._rc(K.sched_call(
+            lib, "csa_dense_bwd_update_head", e.lr_sched_c,
             K.ptr(u.dy), K.ptr(self.views[f"{lp.name}.weight"]), K.ptr(self.views[f"{lp.name}.bias"]),
             K.ptr(prev.dy) if prev is not None else None, B, fin, fout,
             K.ptr(u.x.view(B, -1)), _act_id(tf.act), _alpha(tf.act), *self._bn_args_c(tf),
@@ -2187,7 +2192,8 @@ class HipProgram:
             cursor_args = (K.ptr(e.stream.cursor), e.stream.wrap)
         if getattr(self, "carry", None) is not None:
             lib.csa_optimizer_set_pending(K.ptr(self.carry_pending))
-        self._rc(lib.csa_optimizer2s(
+        self._rc(K.sched_call(
+            lib, "csa_optimizer2s", e.lr_sched_c,
             e.opt_id, K.ptr(w), K.ptr(g), K.ptr(s0), K.ptr(s1), w.numel(), slo, shi, len(segs),
             0 if self.ps_mode else 1, float(e.lr), K.ptr(e.dstep),
             zp, zn, len(zregs), fo, fn, fs, fS, fl, fz, len(folds), klo, khi, len(keep),

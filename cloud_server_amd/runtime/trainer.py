@@ -9,7 +9,7 @@ construct_distribute_url.py (stock MNIST).  Kept behaviour:
   blank line (:405-420).  The URL variant's missing final line (quirk 5) is fixed.
 * resume from the newest checkpoint in ``train_model/`` (Supervisor auto-restore).
 
-New: ``metrics.jsonl`` (step, loss, accuracy, step_ms, samples_per_s), ``status.json``
+New: ``metrics.jsonl`` (step, loss, accuracy, lr, step_ms, samples_per_s), ``status.json``
 (state machine queued -> running -> paused -> stopped | failed | done), a control
 file (``control.json``: stop / pause / resume) polled between log intervals, an
 optional fault-injection hook (``CSA_FAULT_AT_STEP``) for failure-recovery tests, and
@@ -28,6 +28,7 @@ import torch
 
 from ..data.datasets import ArrayDataset, load_dataset_for_model, load_mnist_dir
 from ..models.dsl import parse_train_config
+from ..ops.lr_schedule import lr_at
 from ..parallel.dist import DistContext, all_reduce_max, barrier
 from . import checkpoint as ckpt
 from ..utils.locks import WriterLock
@@ -226,6 +227,9 @@ class _MetricLog:
             if self.chief:
                 self.fr.write("step:%d,accuracy:%f,duration:%f\n" % (step, acc, step_time))
                 self.fm.write(json.dumps({"step": step, "loss": mloss, "accuracy": macc, "batch_accuracy": acc,
+                                          # the rate step `step`'s update ran at (its 1-based t is
+                                          # step + 1; Adam's correction excluded): host arithmetic
+                                          "lr": lr_at(self.eng.cfg, step + 1),
                                           "step_ms": step_time * 1e3,
                                           "samples_per_s": B * self.world / max(step_time, 1e-9),
                                           "comm_ms": self.eng.comm_ms_per_step(),
@@ -441,7 +445,8 @@ class JobRun:
         self.int_start = eng.host_step
         now = time.time()
         if self.chief and (now - self.t_status > 1.0 or self.nlog == 0):
-            write_status(self.model_dir, step=eng.host_step, heartbeat=now)     # watchdog liveness
+            write_status(self.model_dir, step=eng.host_step, heartbeat=now,     # watchdog liveness
+                         lr=lr_at(self.cfg, max(eng.host_step, 1)))           # (of the last step run)
             self.t_status = now
         self.nlog += 1
         if self.cfg.ckpt_every > 0 and step > 0 and step % self.cfg.ckpt_every == 0:
@@ -521,7 +526,7 @@ class JobRun:
         eng.close()                   # peer buffers back to the pool (collective)
         if chief:
             write_status(self.model_dir, state=state, step=eng.host_step, final_accuracy=final_acc,
-                         backend=eng.backend, fallback=eng.fallback_reason)
+                         backend=eng.backend, fallback=eng.fallback_reason, lr=lr_at(self.cfg, max(eng.host_step, 1)))
         self._unlock()
         return {"state": state, "step": eng.host_step, "final_accuracy": final_acc, "backend": eng.backend}
 
