@@ -20,6 +20,10 @@ Reference quirks and how they are handled:
 * the step size never changes in the reference (one ``AdagradOptimizer(1e-4)``):
   ``options.lr_schedule`` adds decay and warm-up as a pure function of the step counter
   (ops/lr_schedule.py); a config without it trains at the constant rate, as before.
+* the reference trains on the stored files only (the offline ``/preprocess/`` "copy twins"
+  are its one augmentation): ``options.augment`` redraws a shift / rotation / zoom / erased
+  rectangle for every training image at every step (ops/augment_ref.py); a config without it
+  trains on the stored images, as before.
 * ``keep_prob`` fed but never used (construct_distribute.py:364-417 feeds 0.5 / 1.0; the
   ``tf.nn.dropout`` line is a comment, construct_distribute_url.py:328): a ``dropout``
   layer is a real layer here; a config without one trains without dropout, as before.
@@ -375,6 +379,49 @@ def parse_lr_schedule(d: Any) -> LrSchedule:
     return LrSchedule(kind, S, r, _as_bool(d.get("staircase", False), where + ".staircase"), alpha, W)
 
 
+@dataclass(frozen=True)
+class Augment:
+    """``options.augment``: random warps of the training images, redrawn every step from
+    (seed, step, dataset row) (ops/augment_ref.py is the definition of the arithmetic)."""
+    shift: int = 0                         # s: dx, dy uniform integers in [-s, s] pixels
+    rotate: int = 0                        # R: angle a uniform integer of degrees in [-R, R]
+    scale: int = 0                         # P: zoom (100 + q) / 100, q uniform integer in [-P, P]
+    erase_prob: float = 0.0                # probability that one rectangle becomes ``fill``
+    erase_max: int = 8                     # E: rectangle height and width uniform in [1, E]
+    fill: int = 0                          # pixels sampled outside the image, erased pixels
+
+
+_AUGMENT_KEYS = ("shift", "rotate", "scale", "erase_prob", "erase_max", "fill")
+_AUGMENT_INT_RANGES = {"shift": (0, 8, 0), "rotate": (0, 45, 0), "scale": (0, 30, 0), "erase_max": (1, 14, 8),
+                       "fill": (0, 255, 0)}
+
+
+def parse_augment(d: Any) -> Augment:
+    """``options.augment`` -> Augment (numbers may be strings).  Every amount zero is the
+    option absent: the default ``Augment()``."""
+    where = "options.augment"
+    if not isinstance(d, dict):
+        raise ConfigError(f"{where} must be an object")
+    unknown = sorted(set(d) - set(_AUGMENT_KEYS))
+    if unknown:
+        raise ConfigError(f"{where}: unknown key(s) {unknown}; valid: {list(_AUGMENT_KEYS)}")
+    vals: Dict[str, Any] = {}
+    for key, (lo, hi, default) in _AUGMENT_INT_RANGES.items():
+        v = _as_whole(d.get(key, default), f"{where}.{key}")
+        if not (lo <= v <= hi):
+            raise ConfigError(f"{where}.{key} must be in {lo}..{hi}")
+        vals[key] = v
+    if isinstance(d.get("erase_prob", 0.0), bool):
+        raise ConfigError(f"{where}.erase_prob: expected float, got {d['erase_prob']!r}")
+    p = _as_float(d.get("erase_prob", 0.0), where + ".erase_prob")
+    if not (0.0 <= p <= 1.0):                       # (a NaN fails both compares)
+        raise ConfigError(f"{where}.erase_prob must be in [0, 1]")
+    aug = Augment(erase_prob=p, **vals)
+    if not (aug.shift or aug.rotate or aug.scale or aug.erase_prob > 0.0):
+        return Augment()
+    return aug
+
+
 @dataclass
 class TrainConfig:
     """The whole ``model.json`` (API.md:306-332) in typed form."""
@@ -398,6 +445,7 @@ class TrainConfig:
     eval_every: int = 0                    # held-out validation sweep every k steps (0 = off)
     eval_batch: int = 256                  # rows per validation batch
     lr_schedule: LrSchedule = LrSchedule()  # decay / warm-up of the rate by the step counter
+    augment: Augment = Augment()           # training-time augmentation (all zero: none)
 
     @property
     def effective_optimizer(self) -> str:
@@ -457,6 +505,7 @@ def parse_train_config(cfg: Union[str, bytes, Dict[str, Any]]) -> TrainConfig:
         eval_every=_as_int(ext.get("eval_every", 0), "eval_every"),
         eval_batch=_as_int(ext.get("eval_batch", 256), "eval_batch"),
         lr_schedule=parse_lr_schedule(ext["lr_schedule"]) if "lr_schedule" in ext else LrSchedule(),
+        augment=parse_augment(ext["augment"]) if "augment" in ext else Augment(),
     )
     if tc.compat_adagrad and tc.lr_schedule.type != "constant":
         # the flag means "the reference's fixed Adagrad 1e-4"

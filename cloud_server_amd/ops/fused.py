@@ -180,6 +180,9 @@ _SIGS = {
     # dropout with counter-RNG masks (dropout.hip; ops/dropout_ref.py is the definition)
     "csa_drop_fwd": (I, [P, P, L, L, L, L, U64, P, P, I, F, I, F, I, P]),
     "csa_drop_bwd": (I, [P, P, P, L, L, L, L, U64, P, I, F, I, F, P]),
+    # training-time augmentation (augment.hip; ops/augment_ref.py is the definition):
+    # (images, rows, cursor, B, H, W, AugParamsC*, aug_seed, step, out, stream)
+    "csa_augment_batch": (I, [P, P, P, I, I, I, P, U64, P, P, P]),
     "csa_xgmi_alloc":(I, [L, C.POINTER(P), P]),
     "csa_xgmi_open": (I, [P, C.POINTER(P)]),
     "csa_xgmi_reuse": (I, [P, L, P]),

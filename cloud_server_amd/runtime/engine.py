@@ -29,7 +29,7 @@ from ..data.datasets import ArrayDataset
 from ..data.stream import BatchStream, DeviceDataset
 from ..models.cnn import DigitNet, build_model, loss_fn
 from ..models.dsl import TrainConfig
-from ..ops import lr_schedule, optim_ref
+from ..ops import augment_ref, lr_schedule, optim_ref
 from ..parallel.dist import DistContext, ranks_share_gpu
 from ..parallel.dp import GradSync
 from ..utils.tracing import trace_range
@@ -61,11 +61,22 @@ class StepProgram:
 class TorchProgram(StepProgram):
     def __init__(self, eng: "TrainEngine"):
         self.e = eng
+        # options.augment: the batch the step trained on, uint8 [B, 784] (ops/augment_ref.py)
+        self.aug_img = None
+        if eng.aug is not None:
+            self.aug_img = torch.zeros(eng.cfg.batch_size, eng.data.images.shape[1], dtype=torch.uint8,
+                                       device=eng.device)
 
     def run(self) -> None:
         e = self.e
         idx = e.stream.current()
-        x, y = e.data.batch(idx)
+        if e.aug is None:
+            x, y = e.data.batch(idx)
+        else:
+            # the gathered uint8 rows, warped for (seed, step, dataset row), before the / 255:
+            # the bytes the HIP program's first launch forms
+            self.aug_img.copy_(augment_ref.augment_torch(e.aug, e.data.images.index_select(0, idx), idx, e.dstep))
+            x, y = self.aug_img.to(torch.float32).mul_(1.0 / 255.0), e.data.labels.index_select(0, idx)
         logits = e.model(x)
         loss = loss_fn(e.cfg.loss_name, logits, y)
         e.flat_grad.zero_()
@@ -135,6 +146,11 @@ class TrainEngine:
         self.data = DeviceDataset(train, self.device)
         self.stream = BatchStream(self.data.n, cfg.batch_size, self.device, seed=cfg.seed,
                                   chunk=stream_chunk, rank=self.ctx.rank, world=self.ctx.world)
+        # training-time augmentation (None: the option is absent or all zero — every path then
+        # runs the code it ran before the option existed)
+        self.aug = augment_ref.make_plan(cfg)
+        if self.aug is not None:
+            augment_ref.check_dataset(self.data.images)
         # device-side counters / metric rings (read by host every log interval)
         self.dstep = torch.zeros(1, dtype=torch.int64, device=self.device)
         # dropout masks are drawn per (step, global batch row): ops/dropout_ref.py

@@ -34,6 +34,11 @@ A ``dropout`` layer is a standalone ``drop`` unit (``dropout.hip``): one launch 
 the mask redrawn from the counter RNG (ops/dropout_ref.py), never stored.  A lone
 activation in front of it rides in the same launches, so the dense layer after it reads a
 plain tensor.  Forward-only programs skip the layer altogether.
+
+``options.augment`` adds one launch in front of the training step (``augment.hip``): this
+step's batch, warped for (seed, step, dataset row) as ops/augment_ref.py defines it, lands in
+``aug_img`` and every training-time reader of the images takes that buffer (``_train_src``).
+Predicting, validation and serving read the stored images.
 """
 from __future__ import annotations
 
@@ -46,7 +51,7 @@ from typing import Dict, List, Optional
 import torch
 
 from ..models.dsl import ActSpec, ConvSpec, DenseSpec, DropoutSpec, LayerPlan, NormSpec, PoolSpec
-from ..ops import dropout_ref
+from ..ops import augment_ref, dropout_ref
 from ..ops import fused as K
 from ..ops import fused as _FK      # (K is shadowed by feature counts inside _alloc)
 from ..ops import optim_ref
@@ -150,6 +155,8 @@ class Unit:
 class HipProgram:
     WGRAD_STRIPES = int(os.environ.get("CSA_WGRAD_STRIPES", "16"))   # (A/B knob; <= 16: the tail's loads)
     FWD_ZERO_MAX = 4          # the pair forward's zero list (conv_pair.hip CP_MAXZ)
+    aug = None                # ops.augment_ref.Plan when options.augment is active
+    aug_img = None            # ... and this step's augmented batch, uint8 [B, 784]
 
     def __init__(self, eng, forward_only: bool = False):
         """``forward_only``: the serving program (``serve.hip_infer``) — the same forward
@@ -230,6 +237,7 @@ class HipProgram:
         self._collect_zero_regions()
         self._zero_now()
         self._plan_stage()
+        self._plan_augment()
         self._plan_grad_buckets()
         self._plan_carry()
         self.opt_segments = self._opt_segments()
@@ -1334,6 +1342,47 @@ class HipProgram:
             return self.stage_img, None, None
         return e.data.images, e.stream.rows, e.stream.cursor
 
+    # ------------------------------------------------------------------ augmentation
+    def _plan_augment(self) -> None:
+        """``options.augment`` (ops/augment_ref.py): the first launch of every training step
+        writes this step's batch, warped for (seed, step, dataset row), into ``aug_img``, and
+        every training-time reader of the images takes ``aug_img`` instead of the dataset
+        (``_train_src``).  The launch reads the dataset through the device cursor and the
+        step counter, so it replays inside graphs like the rest of the step.
+
+        A staged program keeps its in-launch staging copy running: the labels the head
+        reads are staged by the same workgroups, and turning the image half off would change
+        an existing kernel.  ``stage_img`` then has no training-time reader."""
+        e = self.e
+        self.aug = getattr(e, "aug", None)
+        if self.aug is None:
+            return
+        B = self.B
+        self.aug_c = self.aug.to_c()
+        self.aug_img = torch.zeros(B, augment_ref.HW * augment_ref.HW, dtype=torch.uint8, device=e.device)
+        # for readers that take a row table: image b of aug_img is row b of a one-line table
+        self.aug_rows = torch.arange(B, dtype=torch.int64, device=e.device).view(1, B)
+        self.aug_cur = torch.zeros(1, dtype=torch.int64, device=e.device)
+
+    def _augment(self, st) -> None:
+        e = self.e
+        self._rc(self.lib.csa_augment_batch(
+            K.ptr(e.data.images), K.ptr(e.stream.rows), K.ptr(e.stream.cursor), self.B, augment_ref.HW,
+            augment_ref.HW, C.byref(self.aug_c), self.aug.seed, K.ptr(e.dstep), K.ptr(self.aug_img), st),
+            "augment_batch")
+
+    def _train_src(self, table: bool = False):
+        """(images, rows, cursor) for a kernel reading this step's images.  ``table``: the
+        reader needs a row table and a cursor (the raw first conv, the float gather); the
+        pair kernels also take a batch at a fixed address (rows = cursor = None).  Without
+        augmentation, and when predicting, exactly what these readers were handed before."""
+        e = self.e
+        if self.aug is None or getattr(self, "_predicting", False):
+            return (e.data.images, e.stream.rows, e.stream.cursor) if table else self._batch_src()
+        if table:
+            return self.aug_img, self.aug_rows, self.aug_cur
+        return self.aug_img, None, None
+
     def reset_after_warmup(self) -> None:
         self._zero_now()
         if getattr(self, "carry", None) is not None:
@@ -1391,8 +1440,10 @@ class HipProgram:
         # this step's dataset rows = stream.rows[cursor]; the kernels resolve the cursor on
         # device and the optimizer launch advances it (no torch index/add launches).
         rows, cur = e.stream.rows, e.stream.cursor
-        img = e.data.images
+        img, rows_t, cur_t = self._train_src(table=True)     # (a raw first conv's weight gradient)
         V, G = self.views, self.gviews
+        if self.aug is not None:
+            self._augment(st)
         for r in self.zero_early:
             r.zero_()
         if getattr(self, "hfuse", False):
@@ -1570,11 +1621,11 @@ class HipProgram:
                     continue
                 ws = st
                 self._rc(lib.csa_conv_wgrad(
-                    None if raw else K.ptr(u.x), K.ptr(img) if raw else None, K.ptr(rows) if raw else None,
+                    None if raw else K.ptr(u.x), K.ptr(img) if raw else None, K.ptr(rows_t) if raw else None,
                     K.ptr(dc), K.ptr(u.dw_acc), K.ptr(u.db_acc) if sp.bias else None, u.wg_stripes,
                     B, h, w, lp.in_shape.c, sp.kh, sp.kw, sp.stride[0], sp.stride[1], lp.pads[0], lp.pads[2],
                     oh, ow, sp.cout, bn[0], bn[1], bn[2], bn[3], bn[4], bn[5], in_act, in_alpha,
-                    K.ptr(cur) if raw else None, ws), "conv_wgrad")
+                    K.ptr(cur_t) if raw else None, ws), "conv_wgrad")
                 if prev is not None:
                     self._rc(lib.csa_conv_dgrad(
                         K.ptr(dc), K.ptr(V[f"{lp.name}.weight"]), K.ptr(prev.dy), geom,
@@ -1611,16 +1662,15 @@ class HipProgram:
     def _forward(self, st) -> None:
         """Every unit's forward launch (the first half of ``run``; ``predict`` reuses it)."""
         e, lib, B = self.e, self.lib, self.B
-        rows, cur = e.stream.rows, e.stream.cursor
+        img, rows, cur = self._train_src(table=True)
         if self.__dict__.get("x_dense_in") is not None:
             D = self.x_dense_in.shape[1]
             if e.data.images.dtype == torch.uint8 and D % 4 == 0:
-                self._rc(lib.csa_gather_images_f32(K.ptr(e.data.images), K.ptr(rows), K.ptr(cur), B, D,
+                self._rc(lib.csa_gather_images_f32(K.ptr(img), K.ptr(rows), K.ptr(cur), B, D,
                                                    K.ptr(self.x_dense_in), st), "gather_images_f32")
             else:
                 idx = rows.index_select(0, cur).view(-1)
-                self.x_dense_in.copy_(e.data.images.index_select(0, idx).to(torch.float32).mul_(1.0 / 255.0))
-        img = e.data.images
+                self.x_dense_in.copy_(img.index_select(0, idx).to(torch.float32).mul_(1.0 / 255.0))
         V = self.views
         # ---------------- forward ----------------
         pend = None                      # the carried update's pending flag, when fc1's forward clears it
@@ -1628,7 +1678,7 @@ class HipProgram:
             ua, ub = self.units[0], self.units[1]
             nt = self.units[2].in_tf if len(self.units) > 2 else self.head_tf
             oslab = nt.slab if nt.has_bn and not self._eval_bn else None
-            simg, srows, scur = self._batch_src()
+            simg, srows, scur = self._train_src()
             # (the tail program: the dense split-K outputs of this step, zeroed by the pair
             # forward's threads — not when predicting, which zeroes them itself)
             fz = [] if getattr(self, "_predicting", False) else getattr(self, "fwd_zero", [])
@@ -1894,7 +1944,7 @@ class HipProgram:
         if nt.has_bn:
             rm = getattr(self.model, f"bn{nt.norm.index}_mean")
             rv = getattr(self.model, f"bn{nt.norm.index}_var")
-        simg, srows, scur = self._batch_src()
+        simg, srows, scur = self._train_src()
         if getattr(self, "tail", False):
             self._tail_set()
         # this step's forward BatchNorm tables (bn_act_apply wrote them for the dense
