@@ -1024,6 +1024,12 @@ static void dgrad_bands(const ConvGeom& g, int& nbands, int& rows, int& rows_in)
   rows_in = in_rows(rows);
 }
 
+// LDS of the VALU forward: one band of input rows + the whole weight tensor.
+static size_t fwd_valu_lds(const ConvGeom& g, int band_rows_in) {
+  const size_t nin = ((size_t)band_rows_in * g.W * g.Cin + 3) & ~(size_t)3;
+  return (nin + (size_t)g.KH * g.KW * g.Cin * g.Cout) * sizeof(float);
+}
+
 static ConvGeom geom_from(const int* v) {
   return ConvGeom{v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8], v[9], v[10], v[11], v[12]};
 }
@@ -1141,10 +1147,11 @@ CSA_API int csa_conv_fwd(const float* x, const uint8_t* img, const int64_t* idx,
   a.y = y; a.argmax = argmax; a.stat_slab = stat_slab;
   a.det = g_csa_det;
   a.nslab = a.det ? conv_fwd_blocks(a.g, a.pool) : SLAB_ROWS;
+  // (a fused pool keeps its window index in one byte: csa_conv_unit_ok refuses it at plan time)
+  if (a.pool.on && a.pool.KH * a.pool.KW > 256) return -1;
   if (conv_fwd_mfma(a, st)) return (int)hipGetLastError();
   fwd_bands(a.g, a.pool, a.nbands, a.band_rows, a.band_rows_in);
-  const size_t nin = ((size_t)a.band_rows_in * a.g.W * a.g.Cin + 3) & ~(size_t)3;
-  const size_t shm = (nin + (size_t)a.g.KH * a.g.KW * a.g.Cin * a.g.Cout) * sizeof(float);
+  const size_t shm = fwd_valu_lds(a.g, a.band_rows_in);
   if (shm > 150 * 1024) return -2;
   static bool attr = set_lds_attr((const void*)conv_fwd_kernel<CB_T, true>) &&
                      set_lds_attr((const void*)conv_fwd_kernel<CB_T, false>);
@@ -1275,6 +1282,38 @@ CSA_API int csa_conv_wgrad_blocks(const int* geom, int bias) {
                  nullptr, 0, 0.f, nullptr, a, shm))
     return -1;
   return g.B * a.nbands;
+}
+
+// Does `conv [act] [pool]` run as a conv unit?  Host only: exactly the refusals of
+// csa_conv_fwd, csa_conv_wgrad and (a unit that is not the program's first) csa_conv_dgrad /
+// csa_conv_bwd, asked at plan time.  1 = yes; 0 = more than 128 channels on a side; -2 = the
+// weights plus one band do not fit the 150 KB of LDS of the forward (VALU, when the shape is
+// outside the MFMA family), the input gradient or the weight gradient; -3 = a fused pool of
+// more than 256 window positions (its index is kept in one byte).
+CSA_API int csa_conv_unit_ok(const int* geom, const int* pool, int bias, int first) {
+  static const float probe = 0.f;    // (as csa_conv_wgrad_blocks: the plans never read it)
+  float dummy_db = 0.f;
+  const ConvGeom g = geom_from(geom);
+  const PoolGeom p = pool_from(pool);
+  if (g.Cin > 128 || g.Cout > 128) return 0;
+  if (p.on && p.KH * p.KW > 256) return -3;
+  ConvMfmaArgs m;
+  size_t shm;
+  if (!conv_fwd_mfma_plan(g, p, m, shm)) {
+    int nb, rows, rows_in;
+    fwd_bands(g, p, nb, rows, rows_in);
+    if (fwd_valu_lds(g, rows_in) > 150 * 1024) return -2;
+  }
+  ConvWgradArgs w;
+  if (wgrad_args(&probe, nullptr, nullptr, nullptr, nullptr, bias ? &dummy_db : nullptr, 1, g.B, g.H, g.W,
+                 g.Cin, g.KH, g.KW, g.SH, g.SW, g.PT, g.PL, g.OH, g.OW, g.Cout, nullptr, 0, 0.f, 0.f, nullptr,
+                 nullptr, 0, 0.f, nullptr, w, shm))
+    return -2;
+  ConvDgradArgs d;
+  if (!first && dgrad_args(nullptr, nullptr, nullptr, geom, nullptr, 0, 0.f, nullptr, 0, 0.f, 0.f, nullptr,
+                           nullptr, nullptr, d, shm))
+    return -2;
+  return 1;
 }
 
 // dW/db (+)= conv weight gradient, accumulated with atomics into `stripes` copies

@@ -801,6 +801,9 @@ static GConvGeom gconv_geom(const int* v) {
 
 }  // namespace csa
 
+// The refusal of csa_gconv_fwd / _wgrad / _dgrad, asked at plan time (host only).
+CSA_API int csa_gconv_ok(const int* geom) { return gconv_ok(gconv_geom(geom)) ? 1 : 0; }
+
 // geom = [B, H, W, Cin, KH, KW, SH, SW, PT, PL, OH, OW, Cout] (as csa_conv_fwd)
 CSA_API int csa_gconv_fwd_splits(const int* geom) {
   const GConvGeom g = gconv_geom(geom);

@@ -311,10 +311,20 @@ CSA_API int csa_bn_bwd_apply(const float* x, const float* y, const float* dy, fl
   return (int)hipGetLastError();
 }
 
+static bool maxpool_ok(const PoolGeom& p) {
+  return !(p.kh * p.kw > 256 || p.kh < 1 || p.kw < 1 || p.sh < 1 || p.sw < 1);
+}
+
+// The refusal of csa_maxpool_fwd / csa_maxpool_bwd, asked at plan time (host only): the
+// window index is kept in one byte, so a window has at most 256 positions.
+CSA_API int csa_maxpool_ok(const int* g) {
+  return maxpool_ok(PoolGeom{g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7], g[8], g[9], g[10], g[11]}) ? 1 : 0;
+}
+
 // g = {B, H, W, C, kh, kw, sh, sw, pad_top, pad_left, OH, OW}; kh * kw <= 256
 CSA_API int csa_maxpool_fwd(const float* x, float* y, uint8_t* argmax, const int* g, hipStream_t st) {
   PoolGeom p{g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7], g[8], g[9], g[10], g[11]};
-  if (p.kh * p.kw > 256 || p.kh < 1 || p.kw < 1 || p.sh < 1 || p.sw < 1) return -1;
+  if (!maxpool_ok(p)) return -1;
   hipLaunchKernelGGL(maxpool_fwd_kernel, dim3(np_grid((long)p.B * p.OH * p.OW * p.C)), dim3(NP_THREADS), 0, st,
                      x, y, argmax, p);
   return (int)hipGetLastError();
@@ -322,7 +332,7 @@ CSA_API int csa_maxpool_fwd(const float* x, float* y, uint8_t* argmax, const int
 
 CSA_API int csa_maxpool_bwd(const float* dy, const uint8_t* argmax, float* dx, const int* g, hipStream_t st) {
   PoolGeom p{g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7], g[8], g[9], g[10], g[11]};
-  if (p.kh * p.kw > 256 || p.kh < 1 || p.kw < 1 || p.sh < 1 || p.sw < 1) return -1;
+  if (!maxpool_ok(p)) return -1;
   hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(np_grid((long)p.B * p.H * p.W * p.C)), dim3(NP_THREADS), 0, st,
                      dy, argmax, dx, p);
   return (int)hipGetLastError();

@@ -186,7 +186,15 @@ class DigitNet(nn.Module):
                 t = F.pad(t, (pl, pr, pt, pb))
             w = self.p(f"{lp.name}.weight").permute(3, 2, 0, 1)
             b = self.p(f"{lp.name}.bias") if sp.bias else None
-            return F.conv2d(t, w, b, stride=sp.stride).permute(0, 2, 3, 1)
+            stride = tuple(sp.stride)
+            if (sp.kh, sp.kw) == (1, 1) and stride != (1, 1):
+                # A strided 1x1 conv reads only every (sh, sw)-th pixel: subsample, then a
+                # stride-1 conv — the same sums, exactly.  torch 2.10.0+rocm7.0 on the CPU
+                # corrupts the heap in the mkldnn backward of F.conv2d with a 1x1 kernel and
+                # stride (2,1), (1,2) or (2,2) (segfault, or "corrupted size vs. prev_size").
+                t = t[:, :, ::stride[0], ::stride[1]]
+                stride = (1, 1)
+            return F.conv2d(t, w, b, stride=stride).permute(0, 2, 3, 1)
         if isinstance(sp, PoolSpec):
             pt, pb, pl, pr = lp.pads
             t = h.permute(0, 3, 1, 2)

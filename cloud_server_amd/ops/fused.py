@@ -44,6 +44,10 @@ _SIGS = {
     "csa_route_bwd": (I, [P, P, P, P, P, I, F, P, I, F, F, P, P, P, I, P, P, P, P, F, P]),
     "csa_conv_dgrad_nslab": (I, [P]),
     "csa_conv_wgrad_blocks": (I, [P, I]),
+    # the launchers' refusals as host-only predicates (asked by HipProgram._lower)
+    "csa_conv_unit_ok": (I, [P, P, I, I]),
+    "csa_maxpool_ok": (I, [P]),
+    "csa_gconv_ok": (I, [P]),
     "csa_conv_dgrad": (I, [P, P, P, P, P, I, F, P, I, F, F, P, P, P, P]),
     "csa_conv_bwd": (I, [P, P, P, P, P, I, F, P, I, F, F, P, P, P, P, P, I, P]),
     "csa_head": (I, [P, I, I, I, F, P, P, P, P, I, F, P, P, P, P, P, P, P, I, P, P, P]),

@@ -22,6 +22,14 @@ A conv with more than 128 input or output channels (beyond the direct kernels' L
 tables) is a **gconv unit**: forward, input gradient and weight gradient as implicit
 MFMA GEMMs whose loaders gather the im2col / transposed operands on the fly
 (``csa_gconv_*`` in gemm.hip); its activation, pool and norm run as standalone units.
+So is a conv of at most 128 channels a side whose whole weight tensor plus one band of rows
+does not fit the direct kernels' 150 KB of LDS (a 3x3 conv 64 -> 64 already): ``_lower``
+asks ``csa_conv_unit_ok``, the launchers' own refusals as a host-only predicate, and makes
+the layer a gconv unit instead of letting the first step fail.  Every refusal a launcher can
+make on geometry is asked at plan time this way (``csa_conv_unit_ok``, ``csa_maxpool_ok``,
+``csa_gconv_ok``).  A max-pool window of more than 256 positions, fused or standalone, is
+``Unsupported`` (the pool kernels keep the window index in one byte): the engine then runs
+the eager program and says why in ``fallback_reason``.
 
 Layer orders the consumer transform cannot express — a 2-D norm after a dense layer, a
 norm over > 128 channels or directly before the head, a pool that does not directly
@@ -943,17 +951,57 @@ class HipProgram:
                     i += 1
             pending.clear()
 
+        def conv_tail(i: int):
+            """(act, pool, next index) of the ``[act] [pool]`` a conv unit at ``i`` would fuse."""
+            act = pool = None
+            j = i + 1
+            if j < len(layers) and isinstance(layers[j].spec, ActSpec) and _y_ok(layers[j].spec):
+                act = layers[j].spec
+                j += 1
+            if (j < len(layers) and isinstance(layers[j].spec, PoolSpec)
+                    and not (self.det and tuple(layers[j].spec.kernel) != tuple(layers[j].spec.stride))):
+                # (deterministic mode: an overlapping pool's routing adds windows into
+                # dc with atomics — it stays a standalone gather-form pool unit)
+                pool = layers[j]
+                j += 1
+            return act, pool, j
+
+        # every pool kernel, fused or standalone, keeps its window index in one byte
+        for lp in layers:
+            if isinstance(lp.spec, PoolSpec):
+                kh, kw = lp.spec.kernel
+                h, w = lp.in_shape.hw
+                oh, ow = lp.out_shape.hw
+                geom = K.ints([self.B, h, w, lp.in_shape.c, kh, kw, lp.spec.stride[0], lp.spec.stride[1],
+                               lp.pads[0], lp.pads[2], oh, ow])
+                if _opt_call(self.lib, "csa_maxpool_ok", geom) == 0:
+                    raise Unsupported(f"pool layer {lp.name}: a {kh}x{kw} window has {kh * kw} positions, the "
+                                      f"pool kernels' one-byte window index holds at most 256")
+
         i = 0
         while i < len(layers):
             lp = layers[i]
             sp = lp.spec
-            if isinstance(sp, ConvSpec) and (lp.in_shape.c > 128 or sp.cout > 128):
-                # wide conv: implicit-GEMM unit on a materialised input; the act / pool /
-                # norm after it become standalone units
-                materialise()
-                units.append(Unit("gconv", lp))
-                i += 1
-                continue
+            if isinstance(sp, ConvSpec):
+                gconv = lp.in_shape.c > 128 or sp.cout > 128
+                if not gconv:
+                    # the first unit reads the images and has no input gradient
+                    first = not units and as_transform("conv") is not None
+                    rc = _opt_call(self.lib, "csa_conv_unit_ok", self._conv_geom(lp, self.B),
+                                   self._pool_geom(Unit("conv", lp, pool=conv_tail(i)[1])),
+                                   int(bool(sp.bias)), int(first))
+                    # (its weights plus one band of rows exceed the direct kernels' 150 KB of LDS)
+                    gconv = rc is not None and rc != 1
+                if gconv:
+                    # wide conv: implicit-GEMM unit on a materialised input; the act / pool /
+                    # norm after it become standalone units
+                    if _opt_call(self.lib, "csa_gconv_ok", self._conv_geom(lp, self.B)) == 0:
+                        raise Unsupported(f"conv layer {lp.name}: batch x map or taps x channels beyond the "
+                                          f"implicit-GEMM kernels' 2^22 index range")
+                    materialise()
+                    units.append(Unit("gconv", lp))
+                    i += 1
+                    continue
             if isinstance(sp, (ConvSpec, DenseSpec)):
                 kind = "conv" if isinstance(sp, ConvSpec) else "dense"
                 tf = as_transform(kind)
@@ -964,15 +1012,7 @@ class HipProgram:
                 u = Unit(kind, lp, in_tf=tf)
                 j = i + 1
                 if kind == "conv":
-                    if j < len(layers) and isinstance(layers[j].spec, ActSpec) and _y_ok(layers[j].spec):
-                        u.act = layers[j].spec
-                        j += 1
-                    if (j < len(layers) and isinstance(layers[j].spec, PoolSpec)
-                            and not (self.det and tuple(layers[j].spec.kernel) != tuple(layers[j].spec.stride))):
-                        # (deterministic mode: an overlapping pool's routing adds windows into
-                        # dc with atomics — it stays a standalone gather-form pool unit)
-                        u.pool = layers[j]
-                        j += 1
+                    u.act, u.pool, j = conv_tail(i)
                 units.append(u)
                 i = j
             elif isinstance(sp, PoolSpec):
