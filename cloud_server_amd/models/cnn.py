@@ -26,7 +26,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ..ops import dropout_ref
-from .dsl import (ActSpec, ConvSpec, DenseSpec, DropoutSpec, LayerPlan, NetPlan, NormSpec, PoolSpec,
+from .dsl import (ActSpec, AvgPoolSpec, ConvSpec, DenseSpec, DropoutSpec, LayerPlan, NetPlan, NormSpec, PoolSpec,
                   TrainConfig)
 
 
@@ -209,6 +209,27 @@ class DigitNet(nn.Module):
                 cols = F.unfold(t, (kh, kw), stride=sp.stride).view(Bn, Cn, kh * kw, oh * ow)
                 return cols.max(dim=2).values.view(Bn, Cn, oh, ow).permute(0, 2, 3, 1)
             return F.max_pool2d(t, sp.kernel, sp.stride).permute(0, 2, 3, 1)
+        if isinstance(sp, AvgPoolSpec):
+            # tf.nn.avg_pool: the window's sum over a zero-padded tensor, divided by the same
+            # window sum of a padded tensor of ones (the number of in-image taps)
+            pt, pb, pl, pr = lp.pads
+            t = h.permute(0, 3, 1, 2)
+            ones = torch.ones((1, 1) + tuple(t.shape[2:]), dtype=h.dtype, device=h.device)
+            if any(lp.pads):
+                t = F.pad(t, (pl, pr, pt, pb))
+                ones = F.pad(ones, (pl, pr, pt, pb))
+            kh, kw = sp.kernel
+            stride = tuple(sp.stride)
+            if self.deterministic:
+                # gather form, as the max pool above: no atomic backward
+                Bn, Cn, Hn, Wn = t.shape
+                oh, ow = (Hn - kh) // stride[0] + 1, (Wn - kw) // stride[1] + 1
+                tot = F.unfold(t, (kh, kw), stride=stride).view(Bn, Cn, kh * kw, oh * ow).sum(dim=2)
+                cnt = F.unfold(ones, (kh, kw), stride=stride).sum(dim=1).view(1, 1, oh * ow)
+                return (tot / cnt).view(Bn, Cn, oh, ow).permute(0, 2, 3, 1)
+            tot = F.avg_pool2d(t, (kh, kw), stride, divisor_override=1)
+            cnt = F.avg_pool2d(ones, (kh, kw), stride, divisor_override=1)
+            return (tot / cnt).permute(0, 2, 3, 1)
         if isinstance(sp, ActSpec):
             return act_fwd(h, sp)
         if isinstance(sp, DropoutSpec):

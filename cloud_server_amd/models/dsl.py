@@ -24,6 +24,10 @@ Reference quirks and how they are handled:
   are its one augmentation): ``options.augment`` redraws a shift / rotation / zoom / erased
   rectangle for every training image at every step (ops/augment_ref.py); a config without it
   trains on the stored images, as before.
+* the reference only ever builds ``tf.nn.max_pool`` (construct_distribute.py:121-130): a
+  ``pool`` entry takes ``"mode": "avg"`` (``tf.nn.avg_pool``: padding never enters the sum or
+  the divisor) and ``"kernel": "global"`` (the window is the whole input map); an entry
+  without either is the reference's max pool, as before.
 * ``keep_prob`` fed but never used (construct_distribute.py:364-417 feeds 0.5 / 1.0; the
   ``tf.nn.dropout`` line is a comment, construct_distribute_url.py:328): a ``dropout``
   layer is a real layer here; a config without one trains without dropout, as before.
@@ -32,7 +36,7 @@ from __future__ import annotations
 
 import json
 import math
-from dataclasses import dataclass, field, asdict
+from dataclasses import dataclass, field, asdict, replace
 from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
 
 INPUT_HW = 28          # construct_distribute.py:216 — input fixed 28x28x1
@@ -44,6 +48,8 @@ OPTIMIZERS = ("GradientDescentOptimizer", "AdagradOptimizer", "AdamOptimizer", "
 ACTIVATIONS = ("sigmoid", "relu", "leaky_relu")
 INITS = ("norm", "zero", "xavier")
 PADDINGS = ("SAME", "VALID")
+POOL_MODES = ("max", "avg")
+GLOBAL = "global"      # a pool's ``kernel`` and ``stride`` until plan_network knows the map
 LR_SCHEDULES = ("constant", "exponential", "inverse_time", "cosine")
 
 
@@ -108,6 +114,17 @@ class PoolSpec:
 
 
 @dataclass
+class AvgPoolSpec:
+    """``tf.nn.avg_pool``: the sum of a window's in-image taps over their number.  Not a
+    PoolSpec: that class means "max pool with a window argmax" wherever it is tested."""
+    kernel: Tuple[int, int] = (2, 2)
+    stride: Tuple[int, int] = (2, 2)
+    padding: str = "SAME"
+    kind: str = "pool"
+    mode: str = "avg"
+
+
+@dataclass
 class ActSpec:
     func: str = "sigmoid"
     alpha: float = 0.2
@@ -132,7 +149,7 @@ class DropoutSpec:
     kind: str = "dropout"
 
 
-LayerSpec = Union[ConvSpec, PoolSpec, ActSpec, DenseSpec, NormSpec, DropoutSpec]
+LayerSpec = Union[ConvSpec, PoolSpec, AvgPoolSpec, ActSpec, DenseSpec, NormSpec, DropoutSpec]
 
 
 def parse_layer(d: Dict[str, Any], idx: int) -> Optional[LayerSpec]:
@@ -165,6 +182,15 @@ def parse_layer(d: Dict[str, Any], idx: int) -> Optional[LayerSpec]:
                         _as_float(d.get("bias_constant", 0.1), where),
                         _as_float(d.get("stddev_norm", 0.1), where))
     if name == "pool":
+        mode = d.get("mode", "max")
+        if not isinstance(mode, str) or mode not in POOL_MODES:
+            raise ConfigError(f"{where}: mode must be one of {POOL_MODES}")
+        cls = AvgPoolSpec if mode == "avg" else PoolSpec
+        if isinstance(d.get("kernel"), str) and d["kernel"].strip().lower() == GLOBAL:
+            # the whole input map, whatever its size: plan_network fills in the numbers
+            if "stride" in d or "padding" in d:
+                raise ConfigError(f"{where}: kernel 'global' takes no stride or padding")
+            return cls(GLOBAL, GLOBAL, "VALID")
         pad = str(d.get("padding", "SAME")).upper()
         if pad not in PADDINGS:
             raise ConfigError(f"{where}: padding must be SAME or VALID")
@@ -172,7 +198,7 @@ def parse_layer(d: Dict[str, Any], idx: int) -> Optional[LayerSpec]:
         s = _pair(d.get("stride", [2, 2]), where + ".stride")
         if min(k) <= 0 or min(s) <= 0:
             raise ConfigError(f"{where}: kernel/stride must be positive")
-        return PoolSpec(k, s, pad)
+        return cls(k, s, pad)
     if name == "active":
         func = str(d.get("active_func", "sigmoid"))
         if func not in ACTIVATIONS:
@@ -284,9 +310,11 @@ def plan_network(layers: Sequence[LayerSpec], in_hw: int = INPUT_HW, in_c: int =
                 params["bias"] = (sp.cout,)
             out = TensorShape(sp.cout, (oh, ow))
             plans.append(LayerPlan(i, sp, shape, out, (pt, pb, pl, pr), params))
-        elif isinstance(sp, PoolSpec):
+        elif isinstance(sp, (PoolSpec, AvgPoolSpec)):
             if not shape.is_spatial:
                 raise ConfigError(f"layer {i}: pool after a connect layer (input is flat)")
+            if sp.kernel == GLOBAL:
+                sp = replace(sp, kernel=tuple(shape.hw), stride=tuple(shape.hw))
             (h, w), (kh, kw), (sh, sw) = shape.hw, sp.kernel, sp.stride
             if sp.padding == "SAME":
                 oh, pt, pb = same_pads(h, kh, sh)

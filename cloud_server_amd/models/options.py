@@ -13,6 +13,8 @@ CATALOG = {
     "param_init": {"options": ["全零", "正态分布", "Xavier"], "default": "全零"},
     "activation_method": {"options": ["Sigmoid", "ReLU"], "default": "ReLU"},
     "padding_method": {"options": ["SAME", "VALID"], "default": "SAME"},
+    # not in the reference's catalog (it only builds max pools): a pool entry's "mode"
+    "pooling_method": {"options": ["Max", "Average"], "default": "Max"},
 }
 
 DSL_TOKENS = {
@@ -25,6 +27,7 @@ DSL_TOKENS = {
     "全零": "zero", "正态分布": "norm", "Xavier": "xavier",
     "Sigmoid": "sigmoid", "ReLU": "relu",
     "SAME": "SAME", "VALID": "VALID",
+    "Max": "max", "Average": "avg",
 }
 
 

@@ -181,6 +181,11 @@ _SIGS = {
     "csa_bn_bwd_apply": (I, [P, P, P, P, L, I, P, P, I, F, P]),
     "csa_maxpool_fwd": (I, [P, P, P, P, P]),
     "csa_maxpool_bwd": (I, [P, P, P, P, P]),
+    # average pooling (avg_pool.hip): (geom) / () / (x, y, geom, form, stream) / (dy, dx, geom, stream)
+    "csa_avgpool_ok": (I, [P]),
+    "csa_avgpool_wave_taps": (I, []),
+    "csa_avgpool_fwd": (I, [P, P, P, I, P]),
+    "csa_avgpool_bwd": (I, [P, P, P, P]),
     # dropout with counter-RNG masks (dropout.hip; ops/dropout_ref.py is the definition)
     "csa_drop_fwd": (I, [P, P, L, L, L, L, U64, P, P, I, F, I, F, I, P]),
     "csa_drop_bwd": (I, [P, P, P, L, L, L, L, U64, P, I, F, I, F, P]),

@@ -43,6 +43,13 @@ the mask redrawn from the counter RNG (ops/dropout_ref.py), never stored.  A lon
 activation in front of it rides in the same launches, so the dense layer after it reads a
 plain tensor.  Forward-only programs skip the layer altogether.
 
+An average pool (``AvgPoolSpec``: ``"mode": "avg"``, also with ``"kernel": "global"``) is
+always a standalone ``pool`` unit without an argmax (``avg_pool.hip``: one launch each way,
+none backward when the unit is first); ``PoolSpec`` keeps meaning "max pool with a window
+argmax" wherever it is tested, so the conv in front of an average pool fuses no pool and
+``conv conv avgpool`` still forms the pair in its no-pool form.  ``csa_avgpool_ok`` is asked
+at plan time; there is no 256-position limit.
+
 ``options.augment`` adds one launch in front of the training step (``augment.hip``): this
 step's batch, warped for (seed, step, dataset row) as ops/augment_ref.py defines it, lands in
 ``aug_img`` and every training-time reader of the images takes that buffer (``_train_src``).
@@ -58,7 +65,7 @@ from typing import Dict, List, Optional
 
 import torch
 
-from ..models.dsl import ActSpec, ConvSpec, DenseSpec, DropoutSpec, LayerPlan, NormSpec, PoolSpec
+from ..models.dsl import ActSpec, AvgPoolSpec, ConvSpec, DenseSpec, DropoutSpec, LayerPlan, NormSpec, PoolSpec
 from ..ops import augment_ref, dropout_ref
 from ..ops import fused as K
 from ..ops import fused as _FK      # (K is shadowed by feature counts inside _alloc)
@@ -977,6 +984,11 @@ class HipProgram:
                 if _opt_call(self.lib, "csa_maxpool_ok", geom) == 0:
                     raise Unsupported(f"pool layer {lp.name}: a {kh}x{kw} window has {kh * kw} positions, the "
                                       f"pool kernels' one-byte window index holds at most 256")
+            elif isinstance(lp.spec, AvgPoolSpec):
+                # (no index byte: any window; the kernels index their tensors with 32-bit ints)
+                if _opt_call(self.lib, "csa_avgpool_ok", self._pool_geom_full(Unit("pool", lp))) != 1:
+                    raise Unsupported(f"average pool layer {lp.name}: batch x map x channels beyond the "
+                                      f"average-pool kernels' 2^30 index range")
 
         i = 0
         while i < len(layers):
@@ -1015,7 +1027,8 @@ class HipProgram:
                     u.act, u.pool, j = conv_tail(i)
                 units.append(u)
                 i = j
-            elif isinstance(sp, PoolSpec):
+            elif isinstance(sp, (PoolSpec, AvgPoolSpec)):
+                # (an average pool is always a standalone unit: conv_tail fuses max pools only)
                 materialise()                    # pool(act(norm(x))): the transform first
                 units.append(Unit("pool", lp))
                 i += 1
@@ -1086,7 +1099,8 @@ class HipProgram:
             elif u.kind == "pool":
                 ph, pw = lp.out_shape.hw
                 u.y = torch.zeros(B, ph, pw, lp.out_shape.c, **f32)
-                u.argmax = torch.zeros(B, ph, pw, lp.out_shape.c, device=dev, dtype=torch.uint8)
+                if not isinstance(lp.spec, AvgPoolSpec):
+                    u.argmax = torch.zeros(B, ph, pw, lp.out_shape.c, device=dev, dtype=torch.uint8)
             elif u.kind == "gconv":
                 oh, ow = lp.out_shape.hw
                 u.y = torch.zeros(B, oh, ow, lp.spec.cout, **f32)
@@ -1833,6 +1847,9 @@ class HipProgram:
             self._rc(lib.csa_drop_fwd(K.ptr(u.x), K.ptr(u.y), *self._drop_args(u), K.ptr(self.e.dstep),
                                       K.ptr(u.used_step), *self._drop_consts(u), train, st), "drop_fwd")
             return
+        if u.kind == "pool" and isinstance(u.layer.spec, AvgPoolSpec):
+            self._rc(lib.csa_avgpool_fwd(K.ptr(u.x), K.ptr(u.y), self._pool_geom_full(u), 0, st), "avgpool_fwd")
+            return
         if u.kind == "pool":
             self._rc(lib.csa_maxpool_fwd(K.ptr(u.x), K.ptr(u.y), K.ptr(u.argmax), self._pool_geom_full(u), st),
                      "maxpool_fwd")
@@ -1889,6 +1906,10 @@ class HipProgram:
             if dx is not None:
                 self._rc(lib.csa_drop_bwd(K.ptr(u.x), K.ptr(u.dy), K.ptr(dx), *self._drop_args(u),
                                           K.ptr(u.used_step), *self._drop_consts(u), st), "drop_bwd")
+            return
+        if u.kind == "pool" and isinstance(u.layer.spec, AvgPoolSpec):
+            if dx is not None:
+                self._rc(lib.csa_avgpool_bwd(K.ptr(u.dy), K.ptr(dx), self._pool_geom_full(u), st), "avgpool_bwd")
             return
         if u.kind == "pool":
             if dx is not None:
