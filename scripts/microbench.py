@@ -20,25 +20,7 @@ from cloud_server_amd.data.datasets import synthetic_mnist  # noqa: E402
 from cloud_server_amd.models.dsl import SAMPLE_CONFIG, parse_train_config  # noqa: E402
 from cloud_server_amd.ops import fused as K  # noqa: E402
 from cloud_server_amd.runtime.engine import TrainEngine  # noqa: E402
-
-
-class Recorder:
-    """Wraps the ctypes library: records (name, fn, args) of every csa_* call."""
-
-    def __init__(self, lib):
-        self.lib = lib
-        self.calls = []
-
-    def __getattr__(self, name):
-        fn = getattr(self.lib, name)
-        if (not name.startswith("csa_") or name.endswith(("_splits", "_slabs", "_nslab", "_ws", "_ok", "_rows", "_grid"))
-                or name.startswith("csa_set_") or name in ("csa_deterministic", "csa_packed")):
-            return fn
-
-        def wrapped(*args):
-            self.calls.append((name, fn, args))
-            return fn(*args)
-        return wrapped
+from recorder import Recorder  # noqa: E402  (scripts/recorder.py)
 
 
 def main() -> int:
