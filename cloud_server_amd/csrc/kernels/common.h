@@ -121,13 +121,27 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
-// Wave64 sum with DPP inside each row of 16 lanes (quad swaps, half-row and row mirrors:
-// VALU data movement, no LDS round trip) and two cross-row shuffles; every lane gets it.
-__device__ __forceinline__ float wave_sum_dpp(float v) {
+// Sum / max over each row of 16 lanes with DPP (quad swaps, half-row and row mirrors: VALU
+// data movement, no LDS round trip); every lane of the row gets it.
+__device__ __forceinline__ float row16_sum(float v) {
   v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xb1, 0xf, 0xf, false));   // quad_perm 1,0,3,2
   v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x4e, 0xf, 0xf, false));   // quad_perm 2,3,0,1
   v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x141, 0xf, 0xf, false));  // row_half_mirror
   v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x140, 0xf, 0xf, false));  // row_mirror
+  return v;
+}
+
+__device__ __forceinline__ float row16_max(float v) {
+  v = fmaxf(v, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xb1, 0xf, 0xf, false)));
+  v = fmaxf(v, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x4e, 0xf, 0xf, false)));
+  v = fmaxf(v, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x141, 0xf, 0xf, false)));
+  v = fmaxf(v, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x140, 0xf, 0xf, false)));
+  return v;
+}
+
+// Wave64 sum: the row sums and two cross-row shuffles; every lane gets it.
+__device__ __forceinline__ float wave_sum_dpp(float v) {
+  v = row16_sum(v);
   v += __shfl_xor(v, 16, 64);
   v += __shfl_xor(v, 32, 64);
   return v;

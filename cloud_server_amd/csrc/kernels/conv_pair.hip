@@ -1495,15 +1495,6 @@ struct CPVFwdArgs {
 
 __host__ __device__ inline int cpv_txw(const CPGeom& g) { return g.W2 + g.KBw - 1 + g.KAw - 1; }
 
-// 16-lane row sum, every lane gets the total (the idiom of head_dgrad.h's row16_sum)
-__device__ __forceinline__ float cpv_row16_sum(float v) {
-  v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xb1, 0xf, 0xf, false));   // quad_perm 1,0,3,2
-  v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x4e, 0xf, 0xf, false));   // quad_perm 2,3,0,1
-  v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x141, 0xf, 0xf, false));  // row_half_mirror
-  v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x140, 0xf, 0xf, false));  // row_mirror
-  return v;
-}
-
 // Floats behind the c1 tile that conv B's window reads may touch: a pool window whose last
 // row / column lies outside conv B's output (odd H2 / W2 under a ceil-mode pool) reads one
 // tile row further; those positions never enter the max.
@@ -1767,8 +1758,8 @@ __global__ __launch_bounds__(CPV_T) void cpv_fwd_kernel(CPVFwdArgs a, CPZero z, 
       // 0..3 of the row write {s0, s1, q0, q1} — to the slab row when the band's units fill
       // one row, else to LDS for the fold below
       const float v0 = ok ? best0 : 0.f, v1 = ok ? best1 : 0.f;
-      const float s0 = cpv_row16_sum(v0), s1 = cpv_row16_sum(v1);
-      const float q0 = cpv_row16_sum(v0 * v0), q1 = cpv_row16_sum(v1 * v1);
+      const float s0 = row16_sum(v0), s1 = row16_sum(v1);
+      const float q0 = row16_sum(v0 * v0), q1 = row16_sum(v1 * v1);
       if (rowok && lane < 4) {
         const float v = lane == 0 ? s0 : lane == 1 ? s1 : lane == 2 ? q0 : q1;
         if (nur > 1) s_sp[rt * 4 + lane] = v;

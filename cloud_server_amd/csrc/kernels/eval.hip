@@ -7,8 +7,8 @@
 //                    lse - z[y], or MSE sum_j (z_j - onehot_j)^2), stored at the row's GLOBAL
 //                    position g = cursor * M + m when g < n_total (the padded tail of the
 //                    last batch writes nothing).  Two modes, one epilogue:
-//                      fused  (K <= 1024): one 256-thread workgroup per row, the forward half
-//                             of head_row_kernel (head.hip) - no separate logits GEMM;
+//                      fused  (K <= 1024): one 256-thread workgroup per row, the row-logits
+//                             block of head_row_kernel (head_math.h) - no logits GEMM;
 //                      logits (any head):  reads the [M, 10] logits csa_dense_fwd wrote, one
 //                             row per 16-lane group.
 //                    The last workgroup to arrive (agent-scope acq_rel counter, the
@@ -22,14 +22,13 @@
 //
 // No float atomics to global memory; every output is a plain vector store.  The caller
 // zeroes {cursor, arrival counter, result record} with one memset node per sweep.
-#include "common.h"
+#include "head_math.h"
 
 namespace csa {
 
-constexpr int EV_NCLS = 10;
-constexpr int EV_T = 256;
+constexpr int EV_T = HROW_T;
 constexpr int EV_KPT = 4;                 // fused mode: K <= EV_KPT * EV_T
-constexpr int EV_REC_INTS = 2 + EV_NCLS * EV_NCLS;   // {n, correct, conf[100]} then double loss_sum
+constexpr int EV_REC_INTS = 2 + NCLS * NCLS;   // {n, correct, conf[100]} then double loss_sum
 
 struct EvalArgs {
   const float* h; int M, K; int in_act; float in_alpha;      // fused: head input [M, K]
@@ -40,38 +39,13 @@ struct EvalArgs {
   int* row_pred; float* row_loss; int* counter;
 };
 
-__device__ __forceinline__ float group16_max(float v) {
-#pragma unroll
-  for (int o = 8; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ float group16_sum(float v) {
-#pragma unroll
-  for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // One row per 16-lane group: lane j < 10 of the group holds logit j (-inf elsewhere).
 // Every lane of the wave must call (ballot / shuffles); returns the row's prediction and
-// loss term in every lane of the group.
+// loss term in every lane of the group (the dlogit is not kept).
 __device__ __forceinline__ void eval_epilogue(float z, int label, int loss, int& am, float& ls) {
-  const int lane = threadIdx.x & 63, j = lane & 15;
-  const bool cls = j < EV_NCLS;
-  const float mx = group16_max(z);
-  // argmax: lowest class index attaining the max (the reference's tf.argmax)
-  const unsigned long long hit = __ballot(cls && z == mx);
-  const unsigned mine = (unsigned)(hit >> (lane & 48)) & 0xffffu;
-  am = mine ? __builtin_ctz(mine) : 0;
-  float lterm = 0.f;
-  if (loss == 0) {
-    const float e = cls ? __expf(z - mx) : 0.f;
-    const float lse = mx + __logf(group16_sum(e));
-    lterm = (cls && j == label) ? lse - z : 0.f;
-  } else if (cls) {
-    const float t = z - (j == label ? 1.f : 0.f);
-    lterm = t * t;
-  }
-  ls = group16_sum(lterm);
+  const int j = threadIdx.x & 15;
+  float d;
+  head_lane_epilogue<Group16Shfl>(z, j < NCLS, j, label, loss, 0.f, 1, am, d, ls);
 }
 
 // Last arriver advances the cursor for the next launch and re-arms the counter.  Called by
@@ -98,47 +72,23 @@ __device__ __forceinline__ long eval_cursor(const EvalArgs& a) {
 // KPT = k per thread, the smallest that covers K (no clamped duplicate loads of Wh rows)
 template <int KPT>
 __global__ __launch_bounds__(EV_T) void eval_rows_fused_kernel(EvalArgs a) {
-  __shared__ float s_part[EV_T / 64][EV_NCLS];
+  __shared__ float s_part[EV_T / 64][NCLS];
   const int m = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int K = a.K;
   // every load first: this thread's h values and Wh rows (clamped addresses), the bias and
   // the row's label (the cursor -> row -> label chain runs under the h / Wh loads)
-  float hv[KPT], wv[KPT][EV_NCLS];
-#pragma unroll
-  for (int u = 0; u < KPT; ++u) {
-    const int k = min(u * EV_T + tid, K - 1);
-    hv[u] = a.h[(long)m * K + k];
-#pragma unroll
-    for (int j = 0; j < EV_NCLS; j += 2) {
-      const float2 t = *reinterpret_cast<const float2*>(a.w + (long)k * EV_NCLS + j);
-      wv[u][j] = t.x; wv[u][j + 1] = t.y;
-    }
-  }
-  const float bias = lane < EV_NCLS ? a.b[lane] : 0.f;
+  float hv[KPT], wv[KPT][NCLS];
+  head_row_load<KPT>(a.h + (long)m * K, a.w, K, hv, wv);
+  const float bias = lane < NCLS ? a.b[lane] : 0.f;
   const long c = eval_cursor(a);
   const long g = c * a.M + m;
   int label = 0;
   if (wave == 0) label = (int)a.labels[a.rows[g]];
-  float acc[EV_NCLS];
-#pragma unroll
-  for (int j = 0; j < EV_NCLS; ++j) acc[j] = 0.f;
-#pragma unroll
-  for (int u = 0; u < KPT; ++u) {
-    const bool ok = u * EV_T + tid < K;
-    const float v = ok ? act_fwd(hv[u], a.in_act, a.in_alpha) : 0.f;
-#pragma unroll
-    for (int j = 0; j < EV_NCLS; ++j) acc[j] = fmaf(v, wv[u][j], acc[j]);
-  }
-#pragma unroll
-  for (int j = 0; j < EV_NCLS; ++j) {
-    const float t = wave_sum_dpp(acc[j]);
-    if (lane == 0) s_part[wave][j] = t;
-  }
+  head_row_partials<KPT>(hv, wv, K, a.in_act, a.in_alpha, s_part);
   __syncthreads();
   if (wave == 0) {
-    // lane j < 10: logit j (waves folded in fixed order); lanes 0..15 are the row's group
-    float z = -INFINITY;
-    if (lane < EV_NCLS) z = s_part[0][lane] + s_part[1][lane] + s_part[2][lane] + s_part[3][lane] + bias;
+    // lane j < 10: logit j; lanes 0..15 are the row's group
+    const float z = head_row_fold(s_part, lane, bias);
     int am; float ls;
     eval_epilogue(z, label, a.loss, am, ls);
     if (lane == 0 && g < (long)a.n_total) {
@@ -158,7 +108,7 @@ __global__ __launch_bounds__(EV_T) void eval_rows_logits_kernel(EvalArgs a) {
   float z = -INFINITY;
   int label = 0;
   if (row) {
-    if (j < EV_NCLS) z = a.logits[(long)m * EV_NCLS + j];
+    if (j < NCLS) z = a.logits[(long)m * NCLS + j];
     label = (int)a.labels[a.rows[g]];
   }
   int am; float ls;
@@ -177,10 +127,10 @@ struct EvalFinishArgs {
 };
 
 __global__ __launch_bounds__(EV_T) void eval_finish_kernel(EvalFinishArgs a) {
-  __shared__ int s_conf[EV_NCLS * EV_NCLS];
+  __shared__ int s_conf[NCLS * NCLS];
   __shared__ double s_sum[EV_T];
   const int tid = threadIdx.x;
-  for (int i = tid; i < EV_NCLS * EV_NCLS; i += EV_T) s_conf[i] = 0;
+  for (int i = tid; i < NCLS * NCLS; i += EV_T) s_conf[i] = 0;
   __syncthreads();
   // thread t: rows t, t + 256, ... in ascending order (a fixed slice, double accumulation)
   double acc = 0.0;
@@ -188,7 +138,7 @@ __global__ __launch_bounds__(EV_T) void eval_finish_kernel(EvalFinishArgs a) {
     const int p = a.row_pred[g];
     const int y = (int)a.labels[a.rows[g]];
     acc += (double)a.row_loss[g];
-    if (p >= 0 && p < EV_NCLS && y >= 0 && y < EV_NCLS) atomicAdd(&s_conf[y * EV_NCLS + p], 1);
+    if (p >= 0 && p < NCLS && y >= 0 && y < NCLS) atomicAdd(&s_conf[y * NCLS + p], 1);
   }
   s_sum[tid] = acc;
   __syncthreads();
@@ -197,10 +147,10 @@ __global__ __launch_bounds__(EV_T) void eval_finish_kernel(EvalFinishArgs a) {
     if (tid < o) s_sum[tid] += s_sum[tid + o];
     __syncthreads();
   }
-  for (int i = tid; i < EV_NCLS * EV_NCLS; i += EV_T) a.record[2 + i] = s_conf[i];
+  for (int i = tid; i < NCLS * NCLS; i += EV_T) a.record[2 + i] = s_conf[i];
   if (tid == 0) {
     int tr = 0;
-    for (int i = 0; i < EV_NCLS; ++i) tr += s_conf[i * EV_NCLS + i];
+    for (int i = 0; i < NCLS; ++i) tr += s_conf[i * NCLS + i];
     a.record[0] = a.n_total;
     a.record[1] = tr;
     *reinterpret_cast<double*>(a.record + EV_REC_INTS) = s_sum[0];    // byte 408: 8-aligned

@@ -19,10 +19,6 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int HT = 1024;
 constexpr int NW = HT / 64;
-#ifndef CSA_NCLS_DEFINED
-#define CSA_NCLS_DEFINED
-constexpr int NCLS = 10;
-#endif
 constexpr size_t HEAD_LDS_MAX = 150 * 1024;
 
 struct HeadArgs {
@@ -53,34 +49,11 @@ __device__ __forceinline__ void head_loss(const HeadArgs& a, const int64_t* idx,
     float* row = s_log + m * NCLS;
 #pragma unroll
     for (int j = 0; j < NCLS; ++j) row[j] += a.b[j];
-    float mx = row[0];
-    int am = 0;
-#pragma unroll
-    for (int j = 1; j < NCLS; ++j)
-      if (row[j] > mx) { mx = row[j]; am = j; }
-    if (am == y) atomicAdd(s_cor, 1);
     if (a.logits_out) {
 #pragma unroll
       for (int j = 0; j < NCLS; ++j) a.logits_out[m * NCLS + j] = row[j];
     }
-    if (a.loss == 0) {
-      float se = 0.f;
-#pragma unroll
-      for (int j = 0; j < NCLS; ++j) se += __expf(row[j] - mx);
-      const float lse = mx + __logf(se);
-      lsum += lse - row[y];
-      const float inv = a.grad_scale / (float)M;
-#pragma unroll
-      for (int j = 0; j < NCLS; ++j) row[j] = (__expf(row[j] - lse) - (j == y ? 1.f : 0.f)) * inv;
-    } else {
-      const float inv = 2.f * a.grad_scale / (float)(M * NCLS);
-#pragma unroll
-      for (int j = 0; j < NCLS; ++j) {
-        const float d = row[j] - (j == y ? 1.f : 0.f);
-        lsum += d * d;
-        row[j] = d * inv;
-      }
-    }
+    if (head_thread_epilogue(row, row, y, a.loss, a.grad_scale, M, lsum) == y) atomicAdd(s_cor, 1);
   }
   lsum = wave_sum(lsum);
   if (lane == 0) s_red[wave] = lsum;
@@ -129,7 +102,7 @@ __global__ __launch_bounds__(RT) void head_rows_kernel(HeadArgs a, int* ws) {
   float* s_h = s_w + K * NCLS;             // [16][K+1]  T(h) rows
   __shared__ int s_last;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int64_t* idx = a.cursor ? a.idx + a.cursor[0] * M : a.idx;
+  const int64_t* idx = head_rows(a.idx, a.cursor, M);
   int my_label = 0;
   if (tid < mrows) my_label = (int)a.labels[idx[m0 + tid]];
   {  // Wh and the 16 rows of T(h): every load of a thread in flight together
@@ -206,34 +179,11 @@ __global__ __launch_bounds__(RT) void head_rows_kernel(HeadArgs a, int* ws) {
     float* row = s_log + tid * NCLS;
 #pragma unroll
     for (int j = 0; j < NCLS; ++j) row[j] += a.b[j];
-    float mx = row[0];
-    int am = 0;
-#pragma unroll
-    for (int j = 1; j < NCLS; ++j)
-      if (row[j] > mx) { mx = row[j]; am = j; }
-    cor = (am == y);
     if (a.logits_out) {
 #pragma unroll
       for (int j = 0; j < NCLS; ++j) a.logits_out[(long)(m0 + tid) * NCLS + j] = row[j];
     }
-    if (a.loss == 0) {
-      float se = 0.f;
-#pragma unroll
-      for (int j = 0; j < NCLS; ++j) se += __expf(row[j] - mx);
-      const float lse = mx + __logf(se);
-      lsum = lse - row[y];
-      const float inv = a.grad_scale / (float)M;
-#pragma unroll
-      for (int j = 0; j < NCLS; ++j) row[j] = (__expf(row[j] - lse) - (j == y ? 1.f : 0.f)) * inv;
-    } else {
-      const float inv = 2.f * a.grad_scale / (float)(M * NCLS);
-#pragma unroll
-      for (int j = 0; j < NCLS; ++j) {
-        const float d = row[j] - (j == y ? 1.f : 0.f);
-        lsum += d * d;
-        row[j] = d * inv;
-      }
-    }
+    cor = head_thread_epilogue(row, row, y, a.loss, a.grad_scale, M, lsum) == y;
   }
   if (wave == 0) {
     lsum = wave_sum(lsum);
@@ -379,13 +329,7 @@ __global__ __launch_bounds__(256) void head_part_kernel(HeadPartArgs a) {
   float bias[NCLS];                // read first: consumed after the logits
 #pragma unroll
   for (int j = 0; j < NCLS; ++j) bias[j] = a.b[j];
-  if (g == 0 && tid == 0) {
-    *a.step += 1;
-    if (a.adv_cursor) {          // the step's batch is staged: its kernels no longer read the cursor
-      const int64_t c = *a.adv_cursor + 1;
-      *a.adv_cursor = (a.wrap > 0 && c >= a.wrap) ? 0 : c;
-    }
-  }
+  if (g == 0 && tid == 0) head_advance(a.step, a.adv_cursor, a.wrap);
   {
     const int K4 = K >> 2, nh4 = rows * K4, nw4 = (K * NCLS) >> 2, tot = nh4 + nw4;
     const float4* h4 = reinterpret_cast<const float4*>(a.h + (long)m0 * K);
@@ -419,12 +363,7 @@ __global__ __launch_bounds__(256) void head_part_kernel(HeadPartArgs a) {
   // the label chain (cursor -> row index -> label) is only needed after the logits: it is
   // issued after the staging loads so its two dependent round trips overlap them
   int label = 0;
-  if (!a.idx) {                    // staged labels
-    if (tid < rows) label = (int)a.labels[m0 + tid];
-  } else {
-    const int64_t* idx = a.cursor ? a.idx + a.cursor[0] * M : a.idx;
-    if (tid < rows) label = (int)a.labels[idx[m0 + tid]];
-  }
+  if (tid < rows) label = head_label(a.labels, a.idx, a.cursor, M, m0 + tid);
   __syncthreads();
   HEAD_STAMP(2);
   // logits: wave w takes rows w, w+4, ...; lane l owns k = 4l + 256i (one float4 of h and
@@ -462,34 +401,12 @@ __global__ __launch_bounds__(256) void head_part_kernel(HeadPartArgs a) {
     float row[NCLS];
 #pragma unroll
     for (int j = 0; j < NCLS; ++j) row[j] = s_lg[tid * NCLS + j] + bias[j];
-    float mx = row[0];
-    int am = 0;
-#pragma unroll
-    for (int j = 1; j < NCLS; ++j)
-      if (row[j] > mx) { mx = row[j]; am = j; }
     if (a.logits_out) {
 #pragma unroll
       for (int j = 0; j < NCLS; ++j) a.logits_out[(long)(m0 + tid) * NCLS + j] = row[j];
     }
     float ls = 0.f;
-    if (a.loss == 0) {
-      float se = 0.f;
-#pragma unroll
-      for (int j = 0; j < NCLS; ++j) se += __expf(row[j] - mx);
-      const float lse = mx + __logf(se);
-      ls = lse - row[label];
-      const float inv = a.grad_scale / (float)M;
-#pragma unroll
-      for (int j = 0; j < NCLS; ++j) s_dl[tid * NCLS + j] = (__expf(row[j] - lse) - (j == label ? 1.f : 0.f)) * inv;
-    } else {
-      const float inv = 2.f * a.grad_scale / (float)(M * NCLS);
-#pragma unroll
-      for (int j = 0; j < NCLS; ++j) {
-        const float d = row[j] - (j == label ? 1.f : 0.f);
-        ls += d * d;
-        s_dl[tid * NCLS + j] = d * inv;
-      }
-    }
+    const int am = head_thread_epilogue(row, s_dl + tid * NCLS, label, a.loss, a.grad_scale, M, ls);
     s_loss[tid] = ls;
     s_cor[tid] = am == label;
   }
@@ -548,7 +465,7 @@ __global__ __launch_bounds__(256) void head_part_kernel(HeadPartArgs a) {
 // Block 0 advances the device step counter (and the staged batch stream's cursor)
 // before any parameter update of the step reads it.
 // ---------------------------------------------------------------------------------
-constexpr int HR_T = 256;
+constexpr int HR_T = HROW_T;
 constexpr int HR_KPT = 4;               // k per thread at most: K <= 1024
 
 struct HeadRowArgs {
@@ -567,71 +484,22 @@ __global__ __launch_bounds__(HR_T) void head_row_kernel(HeadRowArgs a) {
   __shared__ float s_dl[NCLS];
   const int m = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int K = a.K;
-  if (m == 0 && tid == 0) {
-    *a.step += 1;
-    if (a.adv_cursor) {
-      const int64_t c = *a.adv_cursor + 1;
-      *a.adv_cursor = (a.wrap > 0 && c >= a.wrap) ? 0 : c;
-    }
-  }
+  if (m == 0 && tid == 0) head_advance(a.step, a.adv_cursor, a.wrap);
   // every load first: this thread's h values and Wh rows (clamped addresses), the bias
   // and the row's label (the label chain runs under the h / Wh loads)
   float hv[KPT], wv[KPT][NCLS];
-#pragma unroll
-  for (int u = 0; u < KPT; ++u) {
-    const int k = min(u * HR_T + tid, K - 1);
-    hv[u] = a.h[(long)m * K + k];
-#pragma unroll
-    for (int j = 0; j < NCLS; j += 2) {
-      const float2 t = *reinterpret_cast<const float2*>(a.w + (long)k * NCLS + j);
-      wv[u][j] = t.x; wv[u][j + 1] = t.y;
-    }
-  }
+  head_row_load<KPT>(a.h + (long)m * K, a.w, K, hv, wv);
   float bias = lane < NCLS ? a.b[lane] : 0.f;
   int label = 0;
-  if (wave == 0) {
-    if (!a.idx) label = (int)a.labels[m];
-    else label = (int)a.labels[(a.cursor ? a.idx + a.cursor[0] * a.M : a.idx)[m]];
-  }
-  float acc[NCLS];
-#pragma unroll
-  for (int j = 0; j < NCLS; ++j) acc[j] = 0.f;
-#pragma unroll
-  for (int u = 0; u < KPT; ++u) {
-    const bool ok = u * HR_T + tid < K;
-    hv[u] = ok ? act_fwd(hv[u], a.in_act, a.in_alpha) : 0.f;     // post-activation value
-#pragma unroll
-    for (int j = 0; j < NCLS; ++j) acc[j] = fmaf(hv[u], wv[u][j], acc[j]);
-  }
-#pragma unroll
-  for (int j = 0; j < NCLS; ++j) {
-    const float t = wave_sum_dpp(acc[j]);
-    if (lane == 0) s_part[wave][j] = t;
-  }
+  if (wave == 0) label = head_label(a.labels, a.idx, a.cursor, a.M, m);
+  head_row_partials<KPT>(hv, wv, K, a.in_act, a.in_alpha, s_part);     // hv: post-activation value
   __syncthreads();
   if (wave == 0) {
-    // lane j < 10: logit j (waves folded in fixed order), softmax / mse over the 10 lanes
-    float z = -INFINITY;
-    if (lane < NCLS) z = s_part[0][lane] + s_part[1][lane] + s_part[2][lane] + s_part[3][lane] + bias;
-    const float mx = wave_max(z);
-    // argmax: lowest class index attaining the max (the reference's tf.argmax)
-    const unsigned long long hit = __ballot(lane < NCLS && z == mx);
-    const int am = __builtin_ctzll(hit);
-    float d = 0.f, lterm = 0.f;
-    if (a.loss == 0) {
-      const float e = lane < NCLS ? __expf(z - mx) : 0.f;
-      const float se = wave_sum(e);
-      const float lse = mx + __logf(se);
-      if (lane < NCLS) {
-        d = (__expf(z - lse) - (lane == label ? 1.f : 0.f)) * (a.grad_scale / (float)a.M);
-        lterm = lane == label ? lse - z : 0.f;
-      }
-    } else if (lane < NCLS) {
-      const float t = z - (lane == label ? 1.f : 0.f);
-      lterm = t * t;
-      d = t * (2.f * a.grad_scale / (float)(a.M * NCLS));
-    }
-    const float ls = wave_sum(lterm);
+    // lane j < 10: logit j, softmax / mse over the 10 lanes
+    const float z = head_row_fold(s_part, lane, bias);
+    int am;
+    float d, ls;
+    head_lane_epilogue<Wave64Shfl>(z, lane < NCLS, lane, label, a.loss, a.grad_scale, a.M, am, d, ls);
     if (lane < NCLS) {
       s_dl[lane] = d;
       a.dl[(long)m * NCLS + lane] = d;
@@ -670,7 +538,7 @@ __global__ __launch_bounds__(HT) void head_generic_kernel(HeadArgs a) {
   float* s_red = s_log + a.M * NCLS;
   int* s_cor = (int*)(s_red + 16);
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int64_t* idx = a.cursor ? a.idx + a.cursor[0] * a.M : a.idx;
+  const int64_t* idx = head_rows(a.idx, a.cursor, a.M);
   if (tid == 0) *s_cor = 0;
   for (int m = wave; m < a.M; m += NW) {
     float acc[NCLS];
@@ -733,11 +601,6 @@ CSA_API int csa_head_part_rows(int M, int K) {
   return rg;
 }
 
-CSA_API int csa_head_part2(const float* h, int M, int K, int in_act, float in_alpha, const float* w,
-                           const float* b, const int64_t* labels, const int64_t* idx, const int64_t* cursor,
-                           int loss, float grad_scale, float* dh, float* part, float* mpart, int* mcorr,
-                           float* logits_out, int64_t* step, int64_t* adv_cursor, long wrap, hipStream_t st);
-
 // Row-per-workgroup head (see head_row_kernel): 0 when K is outside its family.
 CSA_API int csa_head_row_ok(int M, int K) { return M >= 1 && K >= 1 && K <= HR_KPT * HR_T && K % 2 == 0 ? 1 : 0; }
 
@@ -752,14 +615,6 @@ CSA_API int csa_head_row(const float* h, int M, int K, int in_act, float in_alph
   else if (K <= 2 * HR_T) hipLaunchKernelGGL(head_row_kernel<2>, dim3((unsigned)M), dim3(HR_T), 0, st, a);
   else hipLaunchKernelGGL(head_row_kernel<HR_KPT>, dim3((unsigned)M), dim3(HR_T), 0, st, a);
   return (int)hipGetLastError();
-}
-
-CSA_API int csa_head_part(const float* h, int M, int K, int in_act, float in_alpha, const float* w,
-                          const float* b, const int64_t* labels, const int64_t* idx, const int64_t* cursor,
-                          int loss, float grad_scale, float* dh, float* part, float* mpart, int* mcorr,
-                          float* logits_out, int64_t* step, hipStream_t st) {
-  return csa_head_part2(h, M, K, in_act, in_alpha, w, b, labels, idx, cursor, loss, grad_scale, dh, part, mpart,
-                        mcorr, logits_out, step, nullptr, 0, st);
 }
 
 // idx == null: labels are the staged [M] labels of the step; adv_cursor != null: block 0

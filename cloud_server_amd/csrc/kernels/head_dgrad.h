@@ -2,14 +2,9 @@
 // own launch (head.hip) and by the fused forward chain (dense_direct.hip: fc1 forward ->
 // fc2 forward -> head_dgrad as one launch with ticket hand-offs).
 #pragma once
-#include "common.h"
+#include "head_math.h"
 
 namespace csa {
-
-#ifndef CSA_NCLS_DEFINED
-#define CSA_NCLS_DEFINED
-constexpr int NCLS = 10;
-#endif
 
 // ---------------------------------------------------------------------------------
 // Head + the LAST dense layer's input gradient in ONE launch (round 4, horizontal-fusion
@@ -45,22 +40,6 @@ struct HeadDgradArgs {
   float* dX;                                                  // [M][K1]
 };
 
-__device__ __forceinline__ float row16_max(float v) {
-  v = fmaxf(v, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xb1, 0xf, 0xf, false)));
-  v = fmaxf(v, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x4e, 0xf, 0xf, false)));
-  v = fmaxf(v, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x141, 0xf, 0xf, false)));
-  v = fmaxf(v, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x140, 0xf, 0xf, false)));
-  return v;
-}
-
-__device__ __forceinline__ float row16_sum(float v) {
-  v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xb1, 0xf, 0xf, false));   // quad_perm 1,0,3,2
-  v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x4e, 0xf, 0xf, false));   // quad_perm 2,3,0,1
-  v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x141, 0xf, 0xf, false));  // row_half_mirror
-  v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x140, 0xf, 0xf, false));  // row_mirror
-  return v;
-}
-
 // KPT = head-input values per thread (Kh <= 256 KPT), KQ = W float4s per thread (Kh = 64 KQ)
 // diagnostics (csa_head_debug, scripts/microbench.py MB_HD): per workgroup b, six
 // s_memrealtime stamps (100 MHz, one clock for every XCD) at [8 + 8 b]: start | head input
@@ -92,13 +71,7 @@ __device__ __forceinline__ void head_dgrad_body(const HeadDgradArgs& a, const in
   const int m0 = rt * HD_R, f0 = fs * HD_FS;
   const int nr = min(HD_R, M - m0);
   HD_STAMP(0);
-  if (bid == 0 && tid == 0) {
-    *a.step += 1;
-    if (a.adv_cursor) {
-      const int64_t c = *a.adv_cursor + 1;
-      *a.adv_cursor = (a.wrap > 0 && c >= a.wrap) ? 0 : c;
-    }
-  }
+  if (bid == 0 && tid == 0) head_advance(a.step, a.adv_cursor, a.wrap);
   // ---- every load first
   const int f = tid >> 4, c = tid & 15;
   const int frow = min(f0 + f, K1 - 1);
@@ -120,11 +93,7 @@ __device__ __forceinline__ void head_dgrad_body(const HeadDgradArgs& a, const in
   }
   const float bias = lane < NCLS ? a.b[lane] : 0.f;
   int label = 0;
-  if (wave < nr) {
-    const int m = m0 + wave;
-    if (!a.idx) label = (int)a.labels[m];
-    else label = (int)a.labels[(a.cursor ? a.idx + a.cursor[0] * a.M : a.idx)[m]];
-  }
+  if (wave < nr) label = head_label(a.labels, a.idx, a.cursor, M, m0 + wave);
   // epilogue operand: lane c < R of feature f stores row m0 + c
   const float xe = (a.x_fwd && c < HD_R) ? a.x_fwd[(long)min(m0 + c, M - 1) * K1 + frow] : 0.f;
   // ---- logits
@@ -196,24 +165,9 @@ __device__ __forceinline__ void head_dgrad_body(const HeadDgradArgs& a, const in
     if (lane < NCLS) z = s_part[0][r][lane] + s_part[1][r][lane] + s_part[2][r][lane] + s_part[3][r][lane] + bias;
     // the 10 classes live in lanes 0..9 (row 0 of the wave): 16-lane DPP reductions, no
     // cross-row shuffles (lanes >= 16 reduce their own rows, unused)
-    const float mx = row16_max(z);
-    const unsigned long long hit = __ballot(lane < NCLS && z == mx);
-    const int am = __builtin_ctzll(hit);       // lowest index attaining the max (tf.argmax)
-    float d = 0.f, lterm = 0.f;
-    if (a.loss == 0) {
-      const float e = lane < NCLS ? __expf(z - mx) : 0.f;
-      const float se = row16_sum(e);
-      const float lse = mx + __logf(se);
-      if (lane < NCLS) {
-        d = (__expf(z - lse) - (lane == label ? 1.f : 0.f)) * (a.grad_scale / (float)M);
-        lterm = lane == label ? lse - z : 0.f;
-      }
-    } else if (lane < NCLS) {
-      const float t = z - (lane == label ? 1.f : 0.f);
-      lterm = t * t;
-      d = t * (2.f * a.grad_scale / (float)(M * NCLS));
-    }
-    const float ls = row16_sum(lterm);
+    int am;
+    float d, ls;
+    head_lane_epilogue<Row16Dpp>(z, lane < NCLS, lane, label, a.loss, a.grad_scale, M, am, d, ls);
     if (lane < NCLS) s_dl[r][lane] = d;
     if (fs == 0) {
       if (lane < NCLS) a.dl[(long)m * NCLS + lane] = d;

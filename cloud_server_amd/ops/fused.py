@@ -142,7 +142,6 @@ _SIGS = {
     "csa_conv_pair_bwd_units": (I, [P, I, P, I]),
     "csa_conv_pair_bwd_units_load": (I, [P, I, P]),
     "csa_conv_pair_bwd_bias_mode": (I, [P, I, I]),
-    "csa_head_part": (I, [P, I, I, I, F, P, P, P, P, P, I, F, P, P, P, P, P, P, P]),
     "csa_head_part2": (I, [P, I, I, I, F, P, P, P, P, P, I, F, P, P, P, P, P, P, P, L, P]),
     "csa_gather_batch": (I, [P, P, P, P, I, L, P, P, P]),
     "csa_gather_images_f32": (I, [P, P, P, I, L, P, P]),

@@ -369,7 +369,7 @@ class Plan:
         layer's backward becomes ``csa_dense_bwd_update`` (dgrad + wgrad + the optimizer
         update of its W rows in one launch, dense_update.hip) and the head writes
         per-row-group partial gradients + metrics that the (now small) optimizer launch
-        folds (``csa_head_part``).  Data parallel (all-reduce / ps) runs the SAME fused
+        folds (``csa_head_part2``).  Data parallel (all-reduce / ps) runs the SAME fused
         launch in gradient mode (``csa_dense_bwd_grad_head``): the dense weight / bias
         gradients are stored whole into the flat gradient for the all-reduce and the flat
         optimizer updates them (``fused_grad``); lowrank forms them from gathered operands."""

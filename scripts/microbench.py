@@ -189,7 +189,7 @@ def main() -> int:
     if os.environ.get("MB_HEAD"):
         dbg = torch.zeros(8, dtype=torch.int64, device="cuda")
         for i, (name, fn, args) in enumerate(rec.calls):
-            if name.startswith("csa_head_part"):
+            if name == "csa_head_part2":
                 for _ in range(3):
                     dbg.zero_()
                     eng.program.lib.csa_head_debug(dbg.data_ptr())
@@ -220,23 +220,24 @@ def main() -> int:
                   f"{float(en.min()):.2f}..{float(en.max()):.2f} us | life mean {float((en - st).mean()):.2f} "
                   f"max {float((en - st).max()):.2f}")
     if os.environ.get("MB_HD"):
-        # head_dgrad: per-workgroup stamps (start | logits | softmax + dh | dX), 100 MHz
+        # head_dgrad: six stamps per workgroup at [8 + 8 b] (start | head input landed |
+        # logits | softmax + dh | dX dot | dX stored), 100 MHz
         for i, (name, fn, args) in enumerate(rec.calls):
             if name != "csa_head_dgrad":
                 continue
             nblk = 4096
-            dbg = torch.zeros(8 + 4 * nblk, dtype=torch.int64, device="cuda")
+            dbg = torch.zeros(8 + 8 * nblk, dtype=torch.int64, device="cuda")
             for _ in range(3):
                 dbg.zero_()
                 eng.program.lib.csa_head_debug(dbg.data_ptr())
                 fn(*args)
                 torch.cuda.synchronize()
                 eng.program.lib.csa_head_debug(None)
-            t = dbg[8:].view(nblk, 4).double().cpu()
+            t = dbg[8:].view(nblk, 8)[:, :6].double().cpu()
             t = t[t[:, 0] > 0]
             t0 = float(t[:, 0].min())
-            st, en = (t[:, 0] - t0) / 100.0, (t[:, 3] - t0) / 100.0
-            ph = (t[:, 1:] - t[:, :-1]) / 100.0
+            st, en = (t[:, 0] - t0) / 100.0, (t[:, 5] - t0) / 100.0
+            ph = (t[:, [2, 3, 5]] - t[:, [0, 2, 3]]) / 100.0
             print(f"{i:2d} {name}: {t.shape[0]} blocks, starts 0..{float(st.max()):.2f} us, ends "
                   f"{float(en.min()):.2f}..{float(en.max()):.2f} us | life mean {float((en - st).mean()):.2f} "
                   f"max {float((en - st).max()):.2f} | phases mean loads+logits {float(ph[:, 0].mean()):.2f} "

@@ -51,7 +51,7 @@ def main():
             "csa_head_row": "head_row_kernel", "csa_dense_bwd_update_head": "dense_bwd_update_kernel",
             "csa_dense_bwd_grad_head": "dense_bwd_update_kernel",
             "csa_bn_act_apply": "bn_act_apply_kernel", "csa_dense_fwd": "gemm_f32_kernel",
-            "csa_head_part": "head_part_kernel", "csa_head_part2": "head_part_kernel", "csa_dense_bwd": "gemm_pair_kernel",
+            "csa_head_part2": "head_part_kernel", "csa_dense_bwd": "gemm_pair_kernel",
             "csa_optimizer2": "optim_kernel", "csa_optimizer2s": "optim_kernel", "csa_dd_fwd": "dd_fwd_kernel",
             "csa_dd_fwd_bn": "dd_fwd_wide_bn_kernel",     # (fc1's forward with the BatchNorm on load)
             "csa_dd_dgrad": "dd_dgrad_kernel",
