@@ -12,6 +12,8 @@
 // Layout: most ops use one workgroup (256 threads = 4 waves) per image, the image
 // staged once in LDS; 28x28 digit batches give N workgroups, so a 1k-image batch
 // already fills all 256 CUs several times over.  Elementwise ops are grid-stride.
+#include <climits>
+
 #include "common.h"
 #include "crng.h"
 
@@ -125,7 +127,10 @@ __global__ __launch_bounds__(IMG_THREADS) void sep_filter_kernel(const uint8_t* 
 }
 
 // ------------------------------------------------------------------ rank filters (P7, P12, P13)
-// op 0: median (REPLICATE border), 1: erode (min over in-bounds), 2: dilate (max).
+// Median (REPLICATE border) is median_kernel<K> below.  op 1: erode (min over the in-image
+// taps), 2: dilate (max); k x k window at offsets -k/2 .. k-1-k/2 (even k too).  The tap
+// loops run over the window clipped to the image, so their length is bounded by H and W
+// whatever k is.
 __global__ __launch_bounds__(IMG_THREADS) void rank_filter_kernel(const uint8_t* __restrict__ in,
                                                                   uint8_t* __restrict__ out, int H, int W,
                                                                   int k, int op) {
@@ -136,34 +141,15 @@ __global__ __launch_bounds__(IMG_THREADS) void rank_filter_kernel(const uint8_t*
   __syncthreads();
   for (int p = threadIdx.x; p < HW; p += IMG_THREADS) {
     const int y = p / W, x = p - y * W;
-    if (op == 0) {
-      // median of k*k (k <= 7): histogram-free rank selection over a register window
-      uint8_t v[49];
-      int n = 0;
-      for (int dy = -r; dy <= r; ++dy)
-        for (int dx = -r; dx <= r; ++dx) v[n++] = s_img[clampi(y + dy, H) * W + clampi(x + dx, W)];
-      const int m = n / 2;
-      int med = 0;
-      for (int i = 0; i < n; ++i) {
-        int lt = 0, le = 0;
-        for (int j = 0; j < n; ++j) { lt += v[j] < v[i]; le += v[j] <= v[i]; }
-        if (lt <= m && m < le) { med = v[i]; break; }
+    const int y0 = max(y - r, 0), y1 = (int)min((long)y - r + k, (long)H);
+    const int x0 = max(x - r, 0), x1 = (int)min((long)x - r + k, (long)W);
+    int acc = op == 1 ? 255 : 0;
+    for (int yy = y0; yy < y1; ++yy)
+      for (int xx = x0; xx < x1; ++xx) {
+        const int s = s_img[yy * W + xx];
+        acc = op == 1 ? min(acc, s) : max(acc, s);
       }
-      out[base + p] = (uint8_t)med;
-    } else {
-      int acc = op == 1 ? 255 : 0;
-      for (int dy = -r; dy < k - r; ++dy) {            // k x k window at offset -k/2 (even k too)
-        const int yy = y + dy;
-        if (yy < 0 || yy >= H) continue;
-        for (int dx = -r; dx < k - r; ++dx) {
-          const int xx = x + dx;
-          if (xx < 0 || xx >= W) continue;
-          const int s = s_img[yy * W + xx];
-          acc = op == 1 ? min(acc, s) : max(acc, s);
-        }
-      }
-      out[base + p] = (uint8_t)acc;
-    }
+    out[base + p] = (uint8_t)acc;
   }
 }
 
@@ -332,8 +318,9 @@ __global__ __launch_bounds__(IMG_THREADS) void nlmeans_kernel(const uint8_t* __r
 // squared differences of the (H+2tr) x (W+2tr) template area are summed with a vertical
 // then a horizontal running 7-window — ~13k integer ops per shift instead of 49 per
 // pixel per shift — and every pixel's weight / accumulator update follows.  Sums are
-// exact integers, the weight is the double exp of the spec.  LDS: padded image (uint8),
-// the difference plane and the vertical sums (int).
+// exact integers; the weight is a float __expf of the float product d2 * inv (the spec
+// takes a double exp), which is why this op is compared at |diff| <= 1 and not exactly.
+// LDS: padded image (uint8), the difference plane and the vertical sums (int).
 __global__ __launch_bounds__(IMG_THREADS) void nlmeans_box_kernel(const uint8_t* __restrict__ in,
                                                                   uint8_t* __restrict__ out, int H, int W,
                                                                   double inv_h2, int tr, int sr) {
@@ -416,19 +403,9 @@ __global__ __launch_bounds__(IMG_THREADS) void nlmeans_box_kernel(const uint8_t*
 }
 
 // ------------------------------------------------------------------ salt & pepper (P9)
-// Coordinates are drawn on the host with the reference RNG order; per image: all salt
-// (255) writes, barrier, then all pepper (0) writes.  Operates in place on ``img``.
-__global__ __launch_bounds__(IMG_THREADS) void salt_pepper_kernel(uint8_t* __restrict__ img, int H, int W,
-                                                                  const int* __restrict__ coords, int m) {
-  const long base = (long)blockIdx.x * H * W;
-  const int* c = coords + (long)blockIdx.x * 4 * m;      // [ys_salt, xs_salt, ys_pep, xs_pep]
-  for (int i = threadIdx.x; i < m; i += IMG_THREADS) img[base + (long)c[i] * W + c[m + i]] = 255;
-  __syncthreads();
-  for (int i = threadIdx.x; i < m; i += IMG_THREADS) img[base + (long)c[2 * m + i] * W + c[3 * m + i]] = 0;
-}
-
-// counter-RNG variant: copies the image, then salt draw j = (y: 2+4j, x: 3+4j) and pepper
-// draw j = (y: 4+4j, x: 5+4j) of image n (all salt, barrier, all pepper)
+// Copies the image, then salt draw j = (y: 2+4j, x: 3+4j) and pepper draw j = (y: 4+4j,
+// x: 5+4j) of image n from the counter RNG: all salt, barrier, all pepper, so pepper wins
+// where the two collide.  Every coordinate is a crng_below(., H) or (., W): inside the image.
 __global__ __launch_bounds__(IMG_THREADS) void salt_pepper_rand_kernel(const uint8_t* __restrict__ in,
                                                                        uint8_t* __restrict__ out, int H, int W,
                                                                        uint64_t seed, int m) {
@@ -494,12 +471,18 @@ static bool big_lds(const void* fn) {
   return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) == hipSuccess;
 }
 
+// The guard every entry point starts with: a positive batch and image, and H*W, formed in
+// 64 bits, at most `max_pix` (the kernels index one image with an int).
+static bool dims_ok(int N, int H, int W, long max_pix = INT_MAX) {
+  return N > 0 && H > 0 && W > 0 && (long)H * W <= max_pix;
+}
+
 }  // namespace csa
 
 using namespace csa;
 
 CSA_API int csa_img_flip(const uint8_t* in, uint8_t* out, int N, int H, int W, int mode, hipStream_t st) {
-  if (N <= 0 || H <= 0 || W <= 0 || mode < 0 || mode > 2 || in == out) return -1;
+  if (!dims_ok(N, H, W) || mode < 0 || mode > 2 || in == out) return -1;
   const long total = (long)N * H * W;
   hipLaunchKernelGGL(flip_kernel, dim3(grid_for(total)), dim3(256), 0, st, in, out, total, H, W, mode);
   return (int)hipGetLastError();
@@ -507,7 +490,7 @@ CSA_API int csa_img_flip(const uint8_t* in, uint8_t* out, int N, int H, int W, i
 
 CSA_API int csa_img_affine(const uint8_t* in, uint8_t* out, int N, int H, int W, const double* alpha,
                            const double* beta, int wrap, hipStream_t st) {
-  if (N <= 0 || H <= 0 || W <= 0) return -1;
+  if (!dims_ok(N, H, W)) return -1;
   const long total = (long)N * H * W;
   hipLaunchKernelGGL(affine_kernel, dim3(grid_for(total)), dim3(256), 0, st, in, out, total, (long)H * W,
                      alpha, beta, wrap);
@@ -516,7 +499,7 @@ CSA_API int csa_img_affine(const uint8_t* in, uint8_t* out, int N, int H, int W,
 
 CSA_API int csa_img_affine_rand(const uint8_t* in, uint8_t* out, int N, int H, int W, unsigned long long seed,
                                 double max_alpha, int max_beta, int wrap, hipStream_t st) {
-  if (N <= 0 || H <= 0 || W <= 0 || max_beta < 0) return -1;
+  if (!dims_ok(N, H, W) || max_beta < 0) return -1;
   const long total = (long)N * H * W;
   hipLaunchKernelGGL(affine_rand_kernel, dim3(grid_for(total)), dim3(256), 0, st, in, out, total, (long)H * W,
                      (uint64_t)seed, max_alpha, max_beta, wrap);
@@ -525,14 +508,14 @@ CSA_API int csa_img_affine_rand(const uint8_t* in, uint8_t* out, int N, int H, i
 
 CSA_API int csa_img_salt_pepper_rand(const uint8_t* in, uint8_t* out, int N, int H, int W, unsigned long long seed,
                                      int m, hipStream_t st) {
-  if (N <= 0 || m < 0 || in == out) return -1;
+  if (!dims_ok(N, H, W) || m < 0 || in == out) return -1;
   hipLaunchKernelGGL(salt_pepper_rand_kernel, dim3(N), dim3(IMG_THREADS), 0, st, in, out, H, W, (uint64_t)seed, m);
   return (int)hipGetLastError();
 }
 
 CSA_API int csa_img_sep_filter(const uint8_t* in, uint8_t* out, int N, int H, int W, const double* taps, int k,
                                hipStream_t st) {
-  if (N <= 0 || H * W > MAX_IMG_PIX / 2 || k < 1 || k > 31 || in == out) return -1;
+  if (!dims_ok(N, H, W, MAX_IMG_PIX / 2) || k < 1 || k > 31 || in == out) return -1;
   static bool attr = big_lds((const void*)sep_filter_kernel);
   (void)attr;
   hipLaunchKernelGGL(sep_filter_kernel, dim3(N), dim3(IMG_THREADS), sizeof(double) * H * W, st, in, out, H, W,
@@ -542,7 +525,7 @@ CSA_API int csa_img_sep_filter(const uint8_t* in, uint8_t* out, int N, int H, in
 
 CSA_API int csa_img_rank_filter(const uint8_t* in, uint8_t* out, int N, int H, int W, int k, int op,
                                 hipStream_t st) {
-  if (N <= 0 || H * W > MAX_IMG_PIX || k < 1 || op < 0 || op > 2 || in == out) return -1;
+  if (!dims_ok(N, H, W, MAX_IMG_PIX) || k < 1 || op < 0 || op > 2 || in == out) return -1;
   if (op == 0 && (k > 7 || (k & 1) == 0)) return -1;
   if (op == 0) {                         // median: register window, unrolled selection
     if (k == 1) hipLaunchKernelGGL(median_kernel<1>, dim3(N), dim3(IMG_THREADS), H * W, st, in, out, H, W);
@@ -556,14 +539,15 @@ CSA_API int csa_img_rank_filter(const uint8_t* in, uint8_t* out, int N, int H, i
 }
 
 CSA_API int csa_img_equalize(const uint8_t* in, uint8_t* out, int N, int H, int W, hipStream_t st) {
-  if (N <= 0 || H <= 0 || W <= 0) return -1;
+  if (!dims_ok(N, H, W)) return -1;
   hipLaunchKernelGGL(equalize_kernel, dim3(N), dim3(IMG_THREADS), 0, st, in, out, H * W);
   return (int)hipGetLastError();
 }
 
 CSA_API int csa_img_clahe(const uint8_t* in, uint8_t* out, int N, int H, int W, int tiles, float clip_limit,
                           hipStream_t st) {
-  if (N <= 0 || tiles < 1 || tiles > CLAHE_MAX_TILES || H < tiles || W < tiles || in == out) return -1;
+  if (!dims_ok(N, H, W) || tiles < 1 || tiles > CLAHE_MAX_TILES || H < tiles || W < tiles || in == out) return -1;
+  if (((long)H + tiles - 1) * ((long)W + tiles - 1) > INT_MAX) return -1;   // bounds the padded PH * PW
   const int th = (H + tiles - 1) / tiles, tw = (W + tiles - 1) / tiles;
   const int c0 = (int)((double)clip_limit * th * tw / 256.0);
   const int clip = clip_limit > 0.f ? (c0 > 1 ? c0 : 1) : 0;
@@ -577,8 +561,9 @@ CSA_API int csa_img_clahe(const uint8_t* in, uint8_t* out, int N, int H, int W, 
 CSA_API int csa_img_nlmeans(const uint8_t* in, uint8_t* out, int N, int H, int W, float h, int template_size,
                             int search_size, hipStream_t st) {
   const int tr = template_size / 2, sr = search_size / 2;
-  if (N <= 0 || h <= 0.f || (H + 2 * (tr + sr)) * (W + 2 * (tr + sr)) > MAX_IMG_PIX || in == out) return -1;
+  if (!dims_ok(N, H, W, MAX_IMG_PIX) || !(h > 0.f) || tr < 0 || sr < 0 || tr > 64 || sr > 64 || in == out) return -1;
   const int pad = tr + sr;
+  if ((long)(H + 2 * pad) * (W + 2 * pad) > MAX_IMG_PIX) return -1;       // the padded image lives in LDS
   if (H * W <= 4 * IMG_THREADS && (H + 2 * tr) * (W + 2 * tr) <= 8 * IMG_THREADS &&
       H * (W + 2 * tr) <= 8 * IMG_THREADS) {     // box-sum kernel's per-thread position tables
     const int AW = W + 2 * tr, AH = H + 2 * tr;
@@ -594,16 +579,11 @@ CSA_API int csa_img_nlmeans(const uint8_t* in, uint8_t* out, int N, int H, int W
   return (int)hipGetLastError();
 }
 
-CSA_API int csa_img_salt_pepper(uint8_t* img, int N, int H, int W, const int* coords, int m, hipStream_t st) {
-  if (N <= 0 || m < 0) return -1;
-  if (m == 0) return 0;
-  hipLaunchKernelGGL(salt_pepper_kernel, dim3(N), dim3(IMG_THREADS), 0, st, img, H, W, coords, m);
-  return (int)hipGetLastError();
-}
-
 CSA_API int csa_img_resize(const uint8_t* in, uint8_t* out, int N, int h, int w, int S, const int* iy,
                            const double* wy, const int* ix, const double* wx, hipStream_t st) {
-  if (N <= 0 || S <= 0 || (long)S * w * 8 > 150 * 1024) return -1;
+  // the row pass [S][w] of doubles lives in LDS: for S = 28 that admits widths up to 685;
+  // a wider batch is resized on the host (preprocess/gpu.py)
+  if (!dims_ok(N, h, w) || S <= 0 || (long)S * w * 8 > 150 * 1024 || in == out) return -1;
   static bool attr = big_lds((const void*)resize_kernel);
   (void)attr;
   hipLaunchKernelGGL(resize_kernel, dim3(N), dim3(IMG_THREADS), sizeof(double) * S * w, st, in, out, h, w, S, iy, wy,

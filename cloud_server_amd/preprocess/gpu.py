@@ -32,7 +32,6 @@ _SIGS = {
     "csa_img_equalize": (C.c_int, [K.P, K.P, K.I, K.I, K.I, K.P]),
     "csa_img_clahe": (C.c_int, [K.P, K.P, K.I, K.I, K.I, K.I, K.F, K.P]),
     "csa_img_nlmeans": (C.c_int, [K.P, K.P, K.I, K.I, K.I, K.F, K.I, K.I, K.P]),
-    "csa_img_salt_pepper": (C.c_int, [K.P, K.I, K.I, K.I, K.P, K.I, K.P]),
     "csa_img_resize": (C.c_int, [K.P, K.P, K.I, K.I, K.I, K.I, K.P, K.P, K.P, K.P, K.P]),
     "csa_img_infer_prep": (C.c_int, [K.P, K.P, K.I, K.P]),
     "csa_img_infer_prep_u8": (C.c_int, [K.P, K.P, K.I, K.P]),
@@ -83,12 +82,30 @@ def _d(arr, dtype) -> torch.Tensor:
     return torch.as_tensor(np.ascontiguousarray(arr), dtype=dtype).to(_dev())
 
 
+RESIZE_LDS_BYTES = 150 * 1024     # csa_img_resize: the [size][w] row pass of doubles lives in LDS
+
+
+def resize_on_device(w: int, size: int = 28) -> bool:
+    """Whether ``csa_img_resize`` takes source width ``w`` (size 28: up to 685 pixels)."""
+    return size * w * 8 <= RESIZE_LDS_BYTES
+
+
 def resize(batch: Batch, size: int = 28) -> Batch:
-    """Bicubic (a=-0.75, REPLICATE) resize of a same-shape batch to size x size."""
+    """Bicubic (a=-0.75, REPLICATE) resize of a same-shape batch to size x size.
+
+    A batch wider than ``resize_on_device`` admits is resized by the spec itself on the
+    host (the pipeline hands over one decoded host image at a time, so there is nothing
+    resident for the device to win); the launcher keeps refusing such a width."""
+    if isinstance(batch, np.ndarray) and not resize_on_device(ops_ref._as_batch(batch).shape[-1], size):
+        return ops_ref.resize(batch, size)
     x = to_device(batch)
     n, h, w = x.shape
-    if (h, w) == (size, size):
+    if n == 0:
+        out = torch.empty(0, size, size, dtype=torch.uint8, device=x.device)
+    elif (h, w) == (size, size):
         out = x.clone()
+    elif not resize_on_device(w, size):
+        out = torch.from_numpy(ops_ref.resize(x.cpu().numpy(), size)).to(x.device)
     else:
         iy, wy = ops_ref._resize_axis_weights(h, size)
         ix, wx = ops_ref._resize_axis_weights(w, size)
@@ -113,11 +130,15 @@ def apply_op(name: str, batch: Batch, value1=None, value2=None, *, mode: str = "
              rng: Optional[np.random.Generator] = None, seed: Optional[int] = None) -> Batch:
     """``ops_ref.apply_op`` on the device.  Returns the same container type as ``batch``."""
     name = ops_ref.OP_MAP.get(name, name)
+    if name not in ops_ref.OP_NAMES:
+        raise ValueError(f"unknown preprocessing op {name!r}")
     lib = _lib()
     x = to_device(batch)
     n, H, W = x.shape
     st = K.stream()
     out = torch.empty_like(x)
+    if n == 0:                         # an empty batch is an empty result, as in ops_ref
+        return _finish(batch, out)
     xp, op = x.data_ptr(), out.data_ptr()
     if name in ("flip_up_down", "flip_left_right", "transpose_image"):
         m = {"flip_up_down": 0, "flip_left_right": 1, "transpose_image": 2}[name]

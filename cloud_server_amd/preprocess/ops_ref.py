@@ -241,7 +241,7 @@ def median_filter(img, k=3, *_):
         raise ValueError("median kernel size must be odd")
     win = _windows(img, k, "edge")
     n, h, w = win.shape[:3]
-    return np.median(win.reshape(n, h, w, -1), axis=3).astype(np.uint8)
+    return np.median(win.reshape(n, h, w, k * k), axis=3).astype(np.uint8)   # (k * k, not -1: n may be 0)
 
 
 def erode(img, k=3, *_):
