@@ -26,8 +26,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ..ops import dropout_ref
-from .dsl import (ActSpec, AvgPoolSpec, ConvSpec, DenseSpec, DropoutSpec, LayerPlan, NetPlan, NormSpec, PoolSpec,
-                  TrainConfig)
+from .dsl import (ActSpec, AvgPoolSpec, ConvSpec, DenseSpec, DropoutSpec, LayerPlan, LrnSpec, NetPlan, NormSpec,
+                  PoolSpec, TrainConfig)
 
 
 def trunc_normal_(t: torch.Tensor, std: float, gen: Optional[torch.Generator] = None) -> torch.Tensor:
@@ -230,6 +230,18 @@ class DigitNet(nn.Module):
             tot = F.avg_pool2d(t, (kh, kw), stride, divisor_override=1)
             cnt = F.avg_pool2d(ones, (kh, kw), stride, divisor_override=1)
             return (tot / cnt).permute(0, 2, 3, 1)
+        if isinstance(sp, LrnSpec):
+            # tf.nn.lrn: the window sum as 2r + 1 shifted adds over zero-padded squares, in
+            # ascending channel order (its backward is shifted adds too: nothing atomic, one
+            # form in normal and deterministic mode).  alpha is not divided by the window size.
+            # (taps beyond C - 1 channels away are all padding: adding their zeros changes no bit)
+            Cn = h.shape[-1]
+            r = min(sp.depth_radius, Cn - 1)
+            sq = F.pad(h * h, (r, r))
+            q = sq[..., 0:Cn]
+            for d in range(1, 2 * r + 1):
+                q = q + sq[..., d:d + Cn]
+            return h * (sp.bias + sp.alpha * q) ** (-sp.beta)
         if isinstance(sp, ActSpec):
             return act_fwd(h, sp)
         if isinstance(sp, DropoutSpec):

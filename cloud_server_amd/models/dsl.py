@@ -31,6 +31,11 @@ Reference quirks and how they are handled:
 * ``keep_prob`` fed but never used (construct_distribute.py:364-417 feeds 0.5 / 1.0; the
   ``tf.nn.dropout`` line is a comment, construct_distribute_url.py:328): a ``dropout``
   layer is a real layer here; a config without one trains without dropout, as before.
+* the reference has no ``tf.nn.lrn`` although the TF1 nets its users copy do (the CIFAR-10
+  tutorial's ``norm1`` / ``norm2``): ``{"layer": "lrn"}`` was an unknown name, silently
+  skipped, so the job trained another network than the one written.  It is a real layer now
+  (``LrnSpec``: ``depth_radius``, ``bias``, ``alpha``, ``beta`` with TF's defaults; alpha is
+  not divided by the window size and the window is clipped to the channels, never padded).
 """
 from __future__ import annotations
 
@@ -149,7 +154,19 @@ class DropoutSpec:
     kind: str = "dropout"
 
 
-LayerSpec = Union[ConvSpec, PoolSpec, AvgPoolSpec, ActSpec, DenseSpec, NormSpec, DropoutSpec]
+@dataclass
+class LrnSpec:
+    """``tf.nn.lrn`` over the channels of a pixel: ``y_c = x_c * s_c ** -beta`` with
+    ``s_c = bias + alpha * sum(x_j ** 2 for |j - c| <= depth_radius)``, the window clipped to
+    the channels (TF's defaults)."""
+    depth_radius: int = 5
+    bias: float = 1.0
+    alpha: float = 1.0
+    beta: float = 0.5
+    kind: str = "lrn"
+
+
+LayerSpec = Union[ConvSpec, PoolSpec, AvgPoolSpec, ActSpec, DenseSpec, NormSpec, DropoutSpec, LrnSpec]
 
 
 def parse_layer(d: Dict[str, Any], idx: int) -> Optional[LayerSpec]:
@@ -218,6 +235,24 @@ def parse_layer(d: Dict[str, Any], idx: int) -> Optional[LayerSpec]:
         if not (0.0 < kp <= 1.0):
             raise ConfigError(f"{where}: keep_prob must be in (0, 1]")
         return DropoutSpec(kp)
+    if name == "lrn":
+        r = _as_whole(d.get("depth_radius", 5), where + ".depth_radius")
+        if not (0 <= r < 2 ** 15):
+            raise ConfigError(f"{where}: depth_radius must be in 0..{2 ** 15 - 1}")
+        vals = {}
+        for key, default in (("bias", 1.0), ("alpha", 1.0), ("beta", 0.5)):
+            if isinstance(d.get(key, default), bool):
+                raise ConfigError(f"{where}.{key}: expected float, got {d[key]!r}")
+            vals[key] = _as_float(d.get(key, default), f"{where}.{key}")
+            if not math.isfinite(vals[key]):
+                raise ConfigError(f"{where}.{key} must be finite")
+        if not vals["bias"] > 0:
+            raise ConfigError(f"{where}.bias must be > 0")
+        if not vals["alpha"] >= 0:
+            raise ConfigError(f"{where}.alpha must be >= 0")
+        if not vals["beta"] > 0:
+            raise ConfigError(f"{where}.beta must be > 0")
+        return LrnSpec(r, vals["bias"], vals["alpha"], vals["beta"])
     return None  # unknown layers are skipped, as in the reference (:208-250)
 
 
@@ -325,6 +360,10 @@ def plan_network(layers: Sequence[LayerSpec], in_hw: int = INPUT_HW, in_c: int =
                 raise ConfigError(f"layer {i}: pool window larger than its {h}x{w} input")
             plans.append(LayerPlan(i, sp, shape, TensorShape(shape.c, (oh, ow)), (pt, pb, pl, pr)))
         elif isinstance(sp, (ActSpec, DropoutSpec)):
+            plans.append(LayerPlan(i, sp, shape, shape))
+        elif isinstance(sp, LrnSpec):
+            if not shape.is_spatial:
+                raise ConfigError(f"layer {i}: lrn after a connect layer (input is flat)")
             plans.append(LayerPlan(i, sp, shape, shape))
         elif isinstance(sp, NormSpec):
             plans.append(LayerPlan(i, sp, shape, shape, params={"scale": (shape.c,), "offset": (shape.c,)}))

@@ -185,6 +185,14 @@ _SIGS = {
     "csa_avgpool_wave_taps": (I, []),
     "csa_avgpool_fwd": (I, [P, P, P, I, P]),
     "csa_avgpool_bwd": (I, [P, P, P, P]),
+    # local response normalisation (lrn.hip), geom = {rows, C, depth_radius}:
+    # (geom, k, alpha, beta) / (C) / () / (x, y, keep, geom, k, alpha, beta, form, stream) /
+    # (x, keep, dy, dx, geom, k, alpha, beta, form, stream)
+    "csa_lrn_ok": (I, [P, F, F, F]),
+    "csa_lrn_row_taps": (I, [I]),
+    "csa_lrn_row_max": (I, []),
+    "csa_lrn_fwd": (I, [P, P, P, P, F, F, F, I, P]),
+    "csa_lrn_bwd": (I, [P, P, P, P, P, F, F, F, I, P]),
     # dropout with counter-RNG masks (dropout.hip; ops/dropout_ref.py is the definition)
     "csa_drop_fwd": (I, [P, P, L, L, L, L, U64, P, P, I, F, I, F, I, P]),
     "csa_drop_bwd": (I, [P, P, P, L, L, L, L, U64, P, I, F, I, F, P]),

@@ -177,6 +177,16 @@ class Buffers:
         return K.ints([self.B, h, w, lp.in_shape.c, sp.kernel[0], sp.kernel[1], sp.stride[0], sp.stride[1],
                        lp.pads[0], lp.pads[2], oh, ow])
 
+    def _lrn_geom(self, lp: LayerPlan):
+        """{rows, C, depth_radius} of an lrn layer: a row is one pixel's channels."""
+        h, w = lp.in_shape.hw
+        return K.ints([self.B * h * w, lp.in_shape.c, lp.spec.depth_radius])
+
+    @staticmethod
+    def _lrn_consts(lp: LayerPlan):
+        sp = lp.spec
+        return (float(sp.bias), float(sp.alpha), float(sp.beta))
+
     @staticmethod
     def _bn_channels(u: Unit) -> int:
         """Channel count of a bn unit: C of an NHWC tensor, the features of a 2-D one."""
@@ -193,7 +203,7 @@ class Buffers:
             u.x = prev.y if prev is not None else None
             if prev is None and u.kind != "conv":
                 # first unit reads no raw images: materialise the gathered float input once
-                # per step (NHWC [B, 28, 28, 1] for a bn / pool unit)
+                # per step (NHWC [B, 28, 28, 1] for a bn / pool / lrn unit)
                 self.x_dense_in = torch.zeros(B, u.layer.in_shape.numel, **f32)
                 ish = u.layer.in_shape
                 u.x = (self.x_dense_in if u.kind == "dense" or not ish.is_spatial
@@ -203,6 +213,9 @@ class Buffers:
                 u.y = torch.zeros_like(u.x)
                 # the step whose mask the forward drew (the backward redraws that one)
                 u.used_step = torch.zeros(1, dtype=torch.int64, device=dev)
+            elif u.kind == "lrn":
+                u.y = torch.zeros_like(u.x)
+                u.lrn_s = None if fo else torch.zeros_like(u.x)
             elif u.kind == "bn":
                 u.y = torch.zeros_like(u.x)
                 ch = self._bn_channels(u)

@@ -50,6 +50,15 @@ argmax" wherever it is tested, so the conv in front of an average pool fuses no 
 ``conv conv avgpool`` still forms the pair in its no-pool form.  ``csa_avgpool_ok`` is asked
 at plan time; there is no 256-position limit.
 
+A local response normalisation (``LrnSpec``: ``{"layer": "lrn"}``, ``tf.nn.lrn``) is always a
+standalone ``lrn`` unit (``lrn.hip``: one launch each way, none backward when the unit is
+first).  Pending norm / act layers are materialised in front of it; a conv in front keeps
+fusing its own ``[act] [pool]`` and ``conv conv pool lrn`` still forms the pair; a norm after
+it has no conv producer and is a standalone ``bn`` unit.  Training programs keep
+``s = bias + alpha * window sum`` (``Unit.lrn_s``) for the backward; forward-only programs keep
+the unit (the layer is active at inference) and keep nothing.  ``csa_lrn_ok`` is asked at plan
+time.
+
 ``options.augment`` adds one launch in front of the training step (``augment.hip``): this
 step's batch, warped for (seed, step, dataset row) as ops/augment_ref.py defines it, lands in
 ``aug_img`` and every training-time reader of the images takes that buffer (``_train_src``).
@@ -66,7 +75,8 @@ from typing import List, Optional
 
 import torch
 
-from ..models.dsl import ActSpec, AvgPoolSpec, ConvSpec, DenseSpec, DropoutSpec, LayerPlan, NormSpec, PoolSpec
+from ..models.dsl import (ActSpec, AvgPoolSpec, ConvSpec, DenseSpec, DropoutSpec, LayerPlan, LrnSpec, NormSpec,
+                          PoolSpec)
 from ..ops import fused as K
 from ..utils.streams import dedicated_stream
 
@@ -151,7 +161,7 @@ class Transform:
 
 @dataclass
 class Unit:
-    kind: str                               # "conv" | "dense" | "gconv" | "bn" | "pool" | "drop"
+    kind: str                               # "conv" | "dense" | "gconv" | "bn" | "pool" | "drop" | "lrn"
     layer: LayerPlan
     act: Optional[ActSpec] = None           # conv: fused output act; bn / drop: applied first
     pool: Optional[LayerPlan] = None        # conv: fused pool
@@ -188,6 +198,8 @@ class Unit:
     bn_slab: Optional[torch.Tensor] = None  # bn: forward statistic rows
     bn_bslab: Optional[torch.Tensor] = None  # bn: backward statistic rows
     bn_k: Optional[torch.Tensor] = None     # bn: backward coefficients [2][C]
+    # lrn units (_alloc)
+    lrn_s: Optional[torch.Tensor] = None    # the forward's bias + alpha * window sum, kept for the backward
 
 
 class Plan:
@@ -292,6 +304,10 @@ class Plan:
                 if _opt_call(self.lib, "csa_avgpool_ok", self._pool_geom_full(Unit("pool", lp))) != 1:
                     raise Unsupported(f"average pool layer {lp.name}: batch x map x channels beyond the "
                                       f"average-pool kernels' 2^30 index range")
+            elif isinstance(lp.spec, LrnSpec):
+                if self.lib.csa_lrn_ok(self._lrn_geom(lp), *self._lrn_consts(lp)) != 1:
+                    raise Unsupported(f"lrn layer {lp.name}: batch x map x channels beyond the lrn kernels' "
+                                      f"2^30 index range, or constants they refuse")
 
         i = 0
         while i < len(layers):
@@ -334,6 +350,11 @@ class Plan:
                 # (an average pool is always a standalone unit: conv_tail fuses max pools only)
                 materialise()                    # pool(act(norm(x))): the transform first
                 units.append(Unit("pool", lp))
+                i += 1
+            elif isinstance(sp, LrnSpec):
+                # always a standalone unit, forward-only programs included (active at inference)
+                materialise()                    # lrn(act(norm(x))): the transform first
+                units.append(Unit("lrn", lp))
                 i += 1
             elif isinstance(sp, DropoutSpec):
                 i += 1

@@ -306,7 +306,7 @@ class HipProgram(Plan, Buffers):
         if self.pair is not None and k < 2:
             if k == 1:
                 self._pair_bwd(st)
-        elif u.kind in ("bn", "pool", "drop"):
+        elif u.kind in ("bn", "pool", "drop", "lrn"):
             self._standalone_bwd(u, prev, st)
         elif u.kind == "gconv":
             self._gconv_bwd(u, prev, st)
@@ -404,7 +404,7 @@ class HipProgram(Plan, Buffers):
         for k, u in enumerate(self.units):
             if self.pair is not None and k < 2:
                 continue
-            if u.kind in ("bn", "pool", "drop"):
+            if u.kind in ("bn", "pool", "drop", "lrn"):
                 self._standalone_fwd(u, st)
                 continue
             if u.kind == "gconv":
@@ -514,6 +514,12 @@ class HipProgram(Plan, Buffers):
             self._rc(lib.csa_drop_fwd(K.ptr(u.x), K.ptr(u.y), *self._drop_args(u), K.ptr(self.e.dstep),
                                       K.ptr(u.used_step), *self._drop_consts(u), train, st), "drop_fwd")
             return
+        if u.kind == "lrn":
+            # (a training program's forward-only pass leaves the step's kept tensor alone)
+            keep = None if self._predicting else u.lrn_s
+            self._rc(lib.csa_lrn_fwd(K.ptr(u.x), K.ptr(u.y), K.ptr(keep), self._lrn_geom(u.layer),
+                                     *self._lrn_consts(u.layer), 0, st), "lrn_fwd")
+            return
         if u.kind == "pool" and isinstance(u.layer.spec, AvgPoolSpec):
             self._rc(lib.csa_avgpool_fwd(K.ptr(u.x), K.ptr(u.y), self._pool_geom_full(u), 0, st), "avgpool_fwd")
             return
@@ -570,6 +576,11 @@ class HipProgram(Plan, Buffers):
             if dx is not None:
                 self._rc(lib.csa_drop_bwd(K.ptr(u.x), K.ptr(u.dy), K.ptr(dx), *self._drop_args(u),
                                           K.ptr(u.used_step), *self._drop_consts(u), st), "drop_bwd")
+            return
+        if u.kind == "lrn":
+            if dx is not None:
+                self._rc(lib.csa_lrn_bwd(K.ptr(u.x), K.ptr(u.lrn_s), K.ptr(u.dy), K.ptr(dx), self._lrn_geom(u.layer),
+                                         *self._lrn_consts(u.layer), 0, st), "lrn_bwd")
             return
         if u.kind == "pool" and isinstance(u.layer.spec, AvgPoolSpec):
             if dx is not None:
