@@ -26,8 +26,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ..ops import dropout_ref
-from .dsl import (ActSpec, AvgPoolSpec, ConvSpec, DenseSpec, DropoutSpec, LayerPlan, LrnSpec, NetPlan, NormSpec,
-                  PoolSpec, TrainConfig)
+from .dsl import (ActSpec, AvgPoolSpec, ConvSpec, DenseSpec, DropoutSpec, GroupNormSpec, LayerPlan, LrnSpec, NetPlan,
+                  NormSpec, PoolSpec, TrainConfig)
 
 
 def trunc_normal_(t: torch.Tensor, std: float, gen: Optional[torch.Generator] = None) -> torch.Tensor:
@@ -94,7 +94,7 @@ def init_params(plan: NetPlan, state: FlatState, seed: int = 0) -> None:
         elif isinstance(sp, DenseSpec):
             trunc_normal_(state.view(f"{lp.name}.weight", host), 0.1, gen)
             state.view(f"{lp.name}.bias", host).fill_(0.1)
-        elif isinstance(sp, NormSpec):
+        elif isinstance(sp, (NormSpec, GroupNormSpec)):
             state.view(f"{lp.name}.scale", host).fill_(1.0)
             state.view(f"{lp.name}.offset", host).zero_()
     trunc_normal_(state.view("head.weight", host), 0.1, gen)
@@ -252,6 +252,17 @@ class DigitNet(nn.Module):
                                                h[0].numel(), sp.keep_prob, self.drop_world, self.drop_rank)
             s = dropout_ref.keep_scale(sp.keep_prob)
             return h * (keep.view(h.shape).to(h.dtype) * s)
+        if isinstance(sp, GroupNormSpec):
+            # every group of every sample on its own, biased centred moments: x as
+            # [B, HW, G, C/G], reduced over HW and C/G (one form in normal and deterministic
+            # mode; no running statistics, nothing registered)
+            Bn, Cn = h.shape[0], h.shape[-1]
+            t = h.reshape(Bn, -1, sp.groups, Cn // sp.groups)
+            mean = t.mean(dim=(1, 3), keepdim=True)
+            d = t - mean
+            var = (d * d).mean(dim=(1, 3), keepdim=True)
+            xhat = (d * torch.rsqrt(var + sp.epsilon)).reshape(h.shape)
+            return xhat * self.p(f"{lp.name}.scale") + self.p(f"{lp.name}.offset")
         if isinstance(sp, NormSpec):
             dims = tuple(range(h.dim() - 1))
             scale, offset = self.p(f"{lp.name}.scale"), self.p(f"{lp.name}.offset")

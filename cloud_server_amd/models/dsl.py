@@ -36,6 +36,11 @@ Reference quirks and how they are handled:
   skipped, so the job trained another network than the one written.  It is a real layer now
   (``LrnSpec``: ``depth_radius``, ``bias``, ``alpha``, ``beta`` with TF's defaults; alpha is
   not divided by the window size and the window is clipped to the channels, never padded).
+* the reference's only normalisation is BatchNorm over the batch.  A ``norm`` entry with
+  ``"mode": "layer" | "group" | "instance"`` normalises every group of every sample on its own
+  (``GroupNormSpec``, ``tf.contrib.layers``' ``layer_norm`` / ``group_norm`` /
+  ``instance_norm``): no running statistics, the same arithmetic in training and inference.
+  Without ``mode`` (or with ``"batch"``) the entry is the reference's BatchNorm as before.
 """
 from __future__ import annotations
 
@@ -54,6 +59,7 @@ ACTIVATIONS = ("sigmoid", "relu", "leaky_relu")
 INITS = ("norm", "zero", "xavier")
 PADDINGS = ("SAME", "VALID")
 POOL_MODES = ("max", "avg")
+NORM_MODES = ("batch", "layer", "group", "instance")
 GLOBAL = "global"      # a pool's ``kernel`` and ``stride`` until plan_network knows the map
 LR_SCHEDULES = ("constant", "exponential", "inverse_time", "cosine")
 
@@ -166,7 +172,21 @@ class LrnSpec:
     kind: str = "lrn"
 
 
-LayerSpec = Union[ConvSpec, PoolSpec, AvgPoolSpec, ActSpec, DenseSpec, NormSpec, DropoutSpec, LrnSpec]
+@dataclass
+class GroupNormSpec:
+    """Normalisation of every group of every sample on its own: with x as ``[B, HW, G, C/G]``
+    and m = HW * C/G, ``y = (x - mean) * rsqrt(var + epsilon) * scale_c + offset_c`` with the
+    biased moments over a group's m elements (TF's).  ``layer`` is G = 1, ``instance`` G = C;
+    ``groups`` is None until plan_network knows C.  Not a NormSpec: that class means
+    "BatchNorm with running statistics" wherever it is tested."""
+    groups: Optional[int] = None
+    epsilon: float = 1e-6                  # tf.contrib.layers.group_norm's
+    mode: str = "layer"
+    kind: str = "norm"
+
+
+LayerSpec = Union[ConvSpec, PoolSpec, AvgPoolSpec, ActSpec, DenseSpec, NormSpec, DropoutSpec, LrnSpec,
+                  GroupNormSpec]
 
 
 def parse_layer(d: Dict[str, Any], idx: int) -> Optional[LayerSpec]:
@@ -229,7 +249,26 @@ def parse_layer(d: Dict[str, Any], idx: int) -> Optional[LayerSpec]:
             raise ConfigError(f"{where}: hidden must be positive")
         return DenseSpec(h)
     if name == "norm":
-        return NormSpec(_as_float(d.get("epsilon", 1e-3), where + ".epsilon"))
+        mode = d.get("mode", "batch")
+        if not isinstance(mode, str) or mode not in NORM_MODES:
+            raise ConfigError(f"{where}: mode must be one of {NORM_MODES}")
+        if mode == "batch":
+            return NormSpec(_as_float(d.get("epsilon", 1e-3), where + ".epsilon"))
+        groups = None
+        if mode == "group":
+            if "groups" not in d:
+                raise ConfigError(f"{where}: mode 'group' needs groups")
+            groups = _as_whole(d["groups"], where + ".groups")
+            if not (1 <= groups < 2 ** 31):
+                raise ConfigError(f"{where}.groups must be a whole number >= 1")
+        elif "groups" in d:
+            raise ConfigError(f"{where}: groups goes with mode 'group' only")
+        if isinstance(d.get("epsilon"), bool):
+            raise ConfigError(f"{where}.epsilon: expected float, got {d['epsilon']!r}")
+        eps = _as_float(d.get("epsilon", 1e-6), where + ".epsilon")
+        if not (math.isfinite(eps) and eps > 0):
+            raise ConfigError(f"{where}.epsilon must be finite and > 0")
+        return GroupNormSpec(groups, eps, mode)
     if name == "dropout":
         kp = _as_float(d.get("keep_prob", 0.5), where + ".keep_prob")
         if not (0.0 < kp <= 1.0):
@@ -366,6 +405,18 @@ def plan_network(layers: Sequence[LayerSpec], in_hw: int = INPUT_HW, in_c: int =
                 raise ConfigError(f"layer {i}: lrn after a connect layer (input is flat)")
             plans.append(LayerPlan(i, sp, shape, shape))
         elif isinstance(sp, NormSpec):
+            plans.append(LayerPlan(i, sp, shape, shape, params={"scale": (shape.c,), "offset": (shape.c,)}))
+        elif isinstance(sp, GroupNormSpec):
+            # (after a connect the input is [B, F]: C means F, the parameters are per feature)
+            if sp.mode == "instance" and not shape.is_spatial:
+                raise ConfigError(f"layer {i}: instance norm after a connect layer (every group would be "
+                                  f"one element)")
+            G = {"layer": 1, "instance": shape.c}.get(sp.mode, sp.groups)
+            if not isinstance(G, int) or isinstance(G, bool) or G < 1:
+                raise ConfigError(f"layer {i}: norm mode {sp.mode!r} needs groups, a whole number >= 1")
+            if shape.c % G:
+                raise ConfigError(f"layer {i}: norm groups {G} does not divide its {shape.c} channels")
+            sp = replace(sp, groups=G)
             plans.append(LayerPlan(i, sp, shape, shape, params={"scale": (shape.c,), "offset": (shape.c,)}))
         elif isinstance(sp, DenseSpec):
             fan_in = shape.numel

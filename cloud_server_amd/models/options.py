@@ -15,6 +15,8 @@ CATALOG = {
     "padding_method": {"options": ["SAME", "VALID"], "default": "SAME"},
     # not in the reference's catalog (it only builds max pools): a pool entry's "mode"
     "pooling_method": {"options": ["Max", "Average"], "default": "Max"},
+    # nor is this one (its only norm is BatchNorm): a norm entry's "mode"
+    "normalization_method": {"options": ["Batch", "Layer", "Group", "Instance"], "default": "Batch"},
 }
 
 DSL_TOKENS = {
@@ -28,6 +30,7 @@ DSL_TOKENS = {
     "Sigmoid": "sigmoid", "ReLU": "relu",
     "SAME": "SAME", "VALID": "VALID",
     "Max": "max", "Average": "avg",
+    "Batch": "batch", "Layer": "layer", "Group": "group", "Instance": "instance",
 }
 
 

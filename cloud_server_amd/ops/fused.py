@@ -193,6 +193,18 @@ _SIGS = {
     "csa_lrn_row_max": (I, []),
     "csa_lrn_fwd": (I, [P, P, P, P, F, F, F, I, P]),
     "csa_lrn_bwd": (I, [P, P, P, P, P, F, F, F, I, P]),
+    # layer / group / instance normalisation (group_norm.hip), geom = {B, HW, C, G}:
+    # (geom) / (geom) / (form) / () /
+    # (x, scale, offset, y, stat, geom, eps, act, alpha, form, stream) /
+    # (x, scale, offset, stat, dy, dx, slab, geom, act, alpha, form, stream) /
+    # (slab, B, C, dscale, doffset, stream)
+    "csa_gn_ok": (I, [P]),
+    "csa_gn_form": (I, [P]),
+    "csa_gn_form_max": (I, [I]),
+    "csa_gn_max_blocks": (I, []),
+    "csa_gn_fwd": (I, [P, P, P, P, P, P, F, I, F, I, P]),
+    "csa_gn_bwd": (I, [P, P, P, P, P, P, P, P, I, F, I, P]),
+    "csa_gn_bwd_params": (I, [P, I, I, P, P, P]),
     # dropout with counter-RNG masks (dropout.hip; ops/dropout_ref.py is the definition)
     "csa_drop_fwd": (I, [P, P, L, L, L, L, U64, P, P, I, F, I, F, I, P]),
     "csa_drop_bwd": (I, [P, P, P, L, L, L, L, U64, P, I, F, I, F, P]),

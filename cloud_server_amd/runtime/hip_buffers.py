@@ -187,6 +187,12 @@ class Buffers:
         sp = lp.spec
         return (float(sp.bias), float(sp.alpha), float(sp.beta))
 
+    def _gn_geom(self, lp: LayerPlan):
+        """{B, HW, C, G} of a layer / group / instance norm; a flat input has HW = 1, C = F."""
+        sh = lp.in_shape
+        hw = sh.hw[0] * sh.hw[1] if sh.is_spatial else 1
+        return K.ints([self.B, hw, sh.c, lp.spec.groups])
+
     @staticmethod
     def _bn_channels(u: Unit) -> int:
         """Channel count of a bn unit: C of an NHWC tensor, the features of a 2-D one."""
@@ -203,7 +209,7 @@ class Buffers:
             u.x = prev.y if prev is not None else None
             if prev is None and u.kind != "conv":
                 # first unit reads no raw images: materialise the gathered float input once
-                # per step (NHWC [B, 28, 28, 1] for a bn / pool / lrn unit)
+                # per step (NHWC [B, 28, 28, 1] for a bn / pool / lrn / gn unit)
                 self.x_dense_in = torch.zeros(B, u.layer.in_shape.numel, **f32)
                 ish = u.layer.in_shape
                 u.x = (self.x_dense_in if u.kind == "dense" or not ish.is_spatial
@@ -216,6 +222,11 @@ class Buffers:
             elif u.kind == "lrn":
                 u.y = torch.zeros_like(u.x)
                 u.lrn_s = None if fo else torch.zeros_like(u.x)
+            elif u.kind == "gn":
+                u.y = torch.zeros_like(u.x)
+                if not fo:                       # (both stored whole every step: no zero regions)
+                    u.gn_stat = torch.zeros(B, lp.spec.groups, 2, **f32)
+                    u.gn_slab = torch.zeros(B, 2, lp.in_shape.c, **f32)
             elif u.kind == "bn":
                 u.y = torch.zeros_like(u.x)
                 ch = self._bn_channels(u)

@@ -59,6 +59,18 @@ it has no conv producer and is a standalone ``bn`` unit.  Training programs keep
 the unit (the layer is active at inference) and keep nothing.  ``csa_lrn_ok`` is asked at plan
 time.
 
+A layer / group / instance normalisation (``GroupNormSpec``: a ``norm`` entry with ``mode``)
+is always a standalone ``gn`` unit (``group_norm.hip``), forward-only programs included: it is
+not a ``NormSpec``, so it never joins ``pending`` and never becomes a consumer transform.
+Pending norm / act layers are materialised in front of it; an ``active`` right behind it rides
+in the unit's launches (``Unit.act``; the backward recomputes the pre-activation from x and the
+kept statistics, so any leaky alpha is fine) and the consumer behind reads a plain tensor.
+Training programs keep ``{mean, rstd}`` per (sample, group) (``Unit.gn_stat``) and a
+``[B][2][C]`` slab of per-sample channel sums (``Unit.gn_slab``), both stored whole every step:
+no zero regions.  The backward launch runs even when the unit is first (no input gradient,
+but the parameter gradients), then ``csa_gn_bwd_params`` stores them into the flat gradient.
+``csa_gn_ok`` is asked at plan time.
+
 ``options.augment`` adds one launch in front of the training step (``augment.hip``): this
 step's batch, warped for (seed, step, dataset row) as ops/augment_ref.py defines it, lands in
 ``aug_img`` and every training-time reader of the images takes that buffer (``_train_src``).
@@ -75,8 +87,8 @@ from typing import List, Optional
 
 import torch
 
-from ..models.dsl import (ActSpec, AvgPoolSpec, ConvSpec, DenseSpec, DropoutSpec, LayerPlan, LrnSpec, NormSpec,
-                          PoolSpec)
+from ..models.dsl import (ActSpec, AvgPoolSpec, ConvSpec, DenseSpec, DropoutSpec, GroupNormSpec, LayerPlan, LrnSpec,
+                          NormSpec, PoolSpec)
 from ..ops import fused as K
 from ..utils.streams import dedicated_stream
 
@@ -161,9 +173,9 @@ class Transform:
 
 @dataclass
 class Unit:
-    kind: str                               # "conv" | "dense" | "gconv" | "bn" | "pool" | "drop" | "lrn"
+    kind: str                               # "conv" | "dense" | "gconv" | "bn" | "pool" | "drop" | "lrn" | "gn"
     layer: LayerPlan
-    act: Optional[ActSpec] = None           # conv: fused output act; bn / drop: applied first
+    act: Optional[ActSpec] = None           # conv: fused output act; bn / drop: applied first; gn: applied last
     pool: Optional[LayerPlan] = None        # conv: fused pool
     in_tf: Transform = field(default_factory=Transform)   # transform of this unit's INPUT
     x: Optional[torch.Tensor] = None        # input tensor (pre-transform), None = raw images
@@ -200,6 +212,9 @@ class Unit:
     bn_k: Optional[torch.Tensor] = None     # bn: backward coefficients [2][C]
     # lrn units (_alloc)
     lrn_s: Optional[torch.Tensor] = None    # the forward's bias + alpha * window sum, kept for the backward
+    # gn units (_alloc)
+    gn_stat: Optional[torch.Tensor] = None  # the forward's {mean, rstd} per (sample, group), kept for the backward
+    gn_slab: Optional[torch.Tensor] = None  # the backward's per-sample channel sums [B][2][C]
 
 
 class Plan:
@@ -308,6 +323,10 @@ class Plan:
                 if self.lib.csa_lrn_ok(self._lrn_geom(lp), *self._lrn_consts(lp)) != 1:
                     raise Unsupported(f"lrn layer {lp.name}: batch x map x channels beyond the lrn kernels' "
                                       f"2^30 index range, or constants they refuse")
+            elif isinstance(lp.spec, GroupNormSpec):
+                if self.lib.csa_gn_ok(self._gn_geom(lp)) != 1:
+                    raise Unsupported(f"norm layer {lp.name}: batch x map x channels beyond the group-norm "
+                                      f"kernels' 2^30 index range")
 
         i = 0
         while i < len(layers):
@@ -356,6 +375,15 @@ class Plan:
                 materialise()                    # lrn(act(norm(x))): the transform first
                 units.append(Unit("lrn", lp))
                 i += 1
+            elif isinstance(sp, GroupNormSpec):
+                # always a standalone unit, forward-only programs included; the activation
+                # right behind it rides in its launches
+                materialise()                    # gn(act(norm(x))): the transform first
+                nxt = layers[i + 1].spec if i + 1 < len(layers) else None
+                act = nxt if isinstance(nxt, ActSpec) else None
+                _act_id(act)
+                units.append(Unit("gn", lp, act=act))
+                i += 2 if act is not None else 1
             elif isinstance(sp, DropoutSpec):
                 i += 1
                 if self.forward_only:
@@ -698,6 +726,10 @@ class Plan:
         >= unit k's main layer is final: a growing contiguous SUFFIX of ``flat_grad``.
         (A norm layer's scale/offset grads come from the route kernel of the conv unit
         BEFORE it, so they join the suffix one unit later — the rule still holds.)
+        (A layer / group / instance norm is a ``gn`` unit whose main layer is the norm itself:
+        its own backward, ``csa_gn_bwd`` then ``csa_gn_bwd_params``, STORES the scale / offset
+        gradients of that layer index before unit k's bucket is issued, and the activation that
+        rides in the unit has no parameters — checked against the launches, the rule holds.)
         Each time the ready suffix has grown by >= ``min_bucket`` bytes it is all-reduced
         on a side stream (captured into the same HIP graph) while the main stream keeps
         computing conv gradients; the optimizer waits for the side stream.  With the

@@ -306,7 +306,7 @@ class HipProgram(Plan, Buffers):
         if self.pair is not None and k < 2:
             if k == 1:
                 self._pair_bwd(st)
-        elif u.kind in ("bn", "pool", "drop", "lrn"):
+        elif u.kind in ("bn", "pool", "drop", "lrn", "gn"):
             self._standalone_bwd(u, prev, st)
         elif u.kind == "gconv":
             self._gconv_bwd(u, prev, st)
@@ -404,7 +404,7 @@ class HipProgram(Plan, Buffers):
         for k, u in enumerate(self.units):
             if self.pair is not None and k < 2:
                 continue
-            if u.kind in ("bn", "pool", "drop", "lrn"):
+            if u.kind in ("bn", "pool", "drop", "lrn", "gn"):
                 self._standalone_fwd(u, st)
                 continue
             if u.kind == "gconv":
@@ -520,6 +520,14 @@ class HipProgram(Plan, Buffers):
             self._rc(lib.csa_lrn_fwd(K.ptr(u.x), K.ptr(u.y), K.ptr(keep), self._lrn_geom(u.layer),
                                      *self._lrn_consts(u.layer), 0, st), "lrn_fwd")
             return
+        if u.kind == "gn":
+            # (a training program's forward-only pass leaves the step's kept statistics alone)
+            nm = u.layer.name
+            stat = None if self._predicting else u.gn_stat
+            self._rc(lib.csa_gn_fwd(K.ptr(u.x), K.ptr(self.views[f"{nm}.scale"]), K.ptr(self.views[f"{nm}.offset"]),
+                                    K.ptr(u.y), K.ptr(stat), self._gn_geom(u.layer), float(u.layer.spec.epsilon),
+                                    _act_id(u.act), _alpha(u.act), 0, st), "gn_fwd")
+            return
         if u.kind == "pool" and isinstance(u.layer.spec, AvgPoolSpec):
             self._rc(lib.csa_avgpool_fwd(K.ptr(u.x), K.ptr(u.y), self._pool_geom_full(u), 0, st), "avgpool_fwd")
             return
@@ -581,6 +589,15 @@ class HipProgram(Plan, Buffers):
             if dx is not None:
                 self._rc(lib.csa_lrn_bwd(K.ptr(u.x), K.ptr(u.lrn_s), K.ptr(u.dy), K.ptr(dx), self._lrn_geom(u.layer),
                                          *self._lrn_consts(u.layer), 0, st), "lrn_bwd")
+            return
+        if u.kind == "gn":
+            # (a first unit has no input gradient and still has parameter gradients)
+            nm, G = u.layer.name, self.gviews
+            self._rc(lib.csa_gn_bwd(K.ptr(u.x), K.ptr(self.views[f"{nm}.scale"]), K.ptr(self.views[f"{nm}.offset"]),
+                                    K.ptr(u.gn_stat), K.ptr(u.dy), K.ptr(dx), K.ptr(u.gn_slab),
+                                    self._gn_geom(u.layer), _act_id(u.act), _alpha(u.act), 0, st), "gn_bwd")
+            self._rc(lib.csa_gn_bwd_params(K.ptr(u.gn_slab), self.B, u.layer.in_shape.c, K.ptr(G[f"{nm}.scale"]),
+                                           K.ptr(G[f"{nm}.offset"]), st), "gn_bwd_params")
             return
         if u.kind == "pool" and isinstance(u.layer.spec, AvgPoolSpec):
             if dx is not None:
