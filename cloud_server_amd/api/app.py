@@ -639,7 +639,7 @@ def create_app(settings: Optional[Settings] = None, executor: Optional[str] = No
     @app.get("/generation/options/next/")
     async def gen_next(request: Request):
         prev = request.query_params.get("layer", "")
-        spatial = ["conv", "pool", "norm", "lrn", "active", "dropout", "connect"]
+        spatial = ["conv", "depthwise", "pool", "norm", "lrn", "active", "dropout", "connect"]
         flat = ["connect", "active", "dropout"]
         return J({"options": flat if prev == "connect" else spatial})
 

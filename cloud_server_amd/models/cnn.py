@@ -26,8 +26,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ..ops import dropout_ref
-from .dsl import (ActSpec, AvgPoolSpec, ConvSpec, DenseSpec, DropoutSpec, GroupNormSpec, LayerPlan, LrnSpec, NetPlan,
-                  NormSpec, PoolSpec, TrainConfig)
+from .dsl import (ActSpec, AvgPoolSpec, ConvSpec, DenseSpec, DepthwiseConvSpec, DropoutSpec, GroupNormSpec, LayerPlan,
+                  LrnSpec, NetPlan, NormSpec, PoolSpec, TrainConfig)
 
 
 def trunc_normal_(t: torch.Tensor, std: float, gen: Optional[torch.Generator] = None) -> torch.Tensor:
@@ -80,7 +80,8 @@ def init_params(plan: NetPlan, state: FlatState, seed: int = 0) -> None:
     host = torch.zeros(state.numel, dtype=torch.float32)
     for lp in plan.layers:
         sp = lp.spec
-        if isinstance(sp, ConvSpec):
+        if isinstance(sp, (ConvSpec, DepthwiseConvSpec)):
+            # (a depthwise weight is [kh, kw, C, M]: the same three initialisers on that shape)
             w = state.view(f"{lp.name}.weight", host)
             if sp.init == "zero":
                 w.zero_()
@@ -195,6 +196,23 @@ class DigitNet(nn.Module):
                 t = t[:, :, ::stride[0], ::stride[1]]
                 stride = (1, 1)
             return F.conv2d(t, w, b, stride=stride).permute(0, 2, 3, 1)
+        if isinstance(sp, DepthwiseConvSpec):
+            # tf.nn.depthwise_conv2d as a grouped conv with groups = C: torch's group of output
+            # channel o is o // M, which is TF's c * M + q order.  One form in normal and
+            # deterministic mode (the CPU backward sums in a fixed order).
+            pt, pb, pl, pr = lp.pads
+            Cn = h.shape[-1]
+            t = h.permute(0, 3, 1, 2)
+            if any(lp.pads):
+                t = F.pad(t, (pl, pr, pt, pb))
+            w = self.p(f"{lp.name}.weight").permute(2, 3, 0, 1).reshape(Cn * sp.mult, 1, sp.kh, sp.kw)
+            b = self.p(f"{lp.name}.bias") if sp.bias else None
+            stride = tuple(sp.stride)
+            if (sp.kh, sp.kw) == (1, 1) and stride != (1, 1):
+                # (the strided 1x1 workaround of the conv branch above)
+                t = t[:, :, ::stride[0], ::stride[1]]
+                stride = (1, 1)
+            return F.conv2d(t, w, b, stride=stride, groups=Cn).permute(0, 2, 3, 1)
         if isinstance(sp, PoolSpec):
             pt, pb, pl, pr = lp.pads
             t = h.permute(0, 3, 1, 2)

@@ -41,6 +41,12 @@ Reference quirks and how they are handled:
   (``GroupNormSpec``, ``tf.contrib.layers``' ``layer_norm`` / ``group_norm`` /
   ``instance_norm``): no running statistics, the same arithmetic in training and inference.
   Without ``mode`` (or with ``"batch"``) the entry is the reference's BatchNorm as before.
+* the reference has no ``tf.nn.depthwise_conv2d`` although the TF1 nets its users copy are
+  built from it (slim's MobileNet, ``separable_conv2d``): ``{"layer": "depthwise"}`` was an
+  unknown name, silently skipped, so the job trained another network than the one written.
+  It is a real layer now (``DepthwiseConvSpec``: ``filter: [kh, kw, M]`` with M the channel
+  multiplier, weight ``[kh, kw, C, M]``, output channel ``c * M + q`` reads input channel c;
+  every other key as a ``conv``'s).  A separable convolution is this layer and a 1x1 ``conv``.
 """
 from __future__ import annotations
 
@@ -117,6 +123,24 @@ class ConvSpec:
 
 
 @dataclass
+class DepthwiseConvSpec:
+    """``tf.nn.depthwise_conv2d``: every input channel c is convolved on its own with ``mult``
+    kernels, weight ``[kh, kw, C, mult]``, output channel ``c * mult + q``.  Not a ConvSpec:
+    that class means "dense convolution" wherever it is tested (the pair plan, ``conv_tail``,
+    the gconv rule)."""
+    kh: int
+    kw: int
+    mult: int = 1
+    stride: Tuple[int, int] = (1, 1)
+    padding: str = "SAME"
+    init: str = "norm"
+    bias: bool = False
+    bias_constant: float = 0.1
+    stddev: float = 0.1
+    kind: str = "depthwise"
+
+
+@dataclass
 class PoolSpec:
     kernel: Tuple[int, int] = (2, 2)
     stride: Tuple[int, int] = (2, 2)
@@ -186,7 +210,7 @@ class GroupNormSpec:
 
 
 LayerSpec = Union[ConvSpec, PoolSpec, AvgPoolSpec, ActSpec, DenseSpec, NormSpec, DropoutSpec, LrnSpec,
-                  GroupNormSpec]
+                  GroupNormSpec, DepthwiseConvSpec]
 
 
 def parse_layer(d: Dict[str, Any], idx: int) -> Optional[LayerSpec]:
@@ -218,6 +242,29 @@ def parse_layer(d: Dict[str, Any], idx: int) -> Optional[LayerSpec]:
         return ConvSpec(kh, kw, cout, stride, pad, init, bias,
                         _as_float(d.get("bias_constant", 0.1), where),
                         _as_float(d.get("stddev_norm", 0.1), where))
+    if name == "depthwise":
+        # conv's keys, defaults and quirks; ``filter`` is [kh, kw, channel multiplier]
+        if "filter" not in d:
+            raise ConfigError(f"{where}: depthwise needs 'filter': [kh, kw, multiplier]")
+        f = d["filter"]
+        if not isinstance(f, (list, tuple)) or len(f) != 3:
+            raise ConfigError(f"{where}: depthwise filter must be [kh, kw, multiplier]")
+        kh, kw, mult = (_as_int(x, where + ".filter") for x in f)
+        if min(kh, kw, mult) <= 0:
+            raise ConfigError(f"{where}: depthwise filter dims and multiplier must be positive")
+        pad = str(d.get("padding", "SAME")).upper()
+        init = str(d.get("init", "norm"))
+        if pad not in PADDINGS:
+            raise ConfigError(f"{where}: depthwise padding must be SAME or VALID")
+        if init not in INITS:
+            raise ConfigError(f"{where}: depthwise init must be one of {INITS}")
+        stride = _pair(d.get("stride", [1, 1]), where + ".stride")
+        if min(stride) <= 0:
+            raise ConfigError(f"{where}: depthwise stride must be positive")
+        bias = ("isBias" in d) and (d["isBias"] != "False") and (d["isBias"] is not False)
+        return DepthwiseConvSpec(kh, kw, mult, stride, pad, init, bias,
+                                 _as_float(d.get("bias_constant", 0.1), where),
+                                 _as_float(d.get("stddev_norm", 0.1), where))
     if name == "pool":
         mode = d.get("mode", "max")
         if not isinstance(mode, str) or mode not in POOL_MODES:
@@ -356,6 +403,9 @@ class NetPlan:
             if isinstance(sp, ConvSpec):
                 oh, ow = lp.out_shape.hw
                 f += 2 * oh * ow * sp.cout * sp.kh * sp.kw * lp.in_shape.c
+            elif isinstance(sp, DepthwiseConvSpec):
+                oh, ow = lp.out_shape.hw
+                f += 2 * oh * ow * lp.out_shape.c * sp.kh * sp.kw
             elif isinstance(sp, DenseSpec):
                 f += 2 * lp.in_shape.numel * sp.hidden
         f += 2 * self.head_in * self.num_classes
@@ -384,6 +434,22 @@ def plan_network(layers: Sequence[LayerSpec], in_hw: int = INPUT_HW, in_c: int =
                 params["bias"] = (sp.cout,)
             out = TensorShape(sp.cout, (oh, ow))
             plans.append(LayerPlan(i, sp, shape, out, (pt, pb, pl, pr), params))
+        elif isinstance(sp, DepthwiseConvSpec):
+            if not shape.is_spatial:
+                raise ConfigError(f"layer {i}: depthwise after a connect layer (input is flat)")
+            (h, w), (sh, sw) = shape.hw, sp.stride
+            if sp.padding == "SAME":
+                oh, pt, pb = same_pads(h, sp.kh, sh)
+                ow, pl, pr = same_pads(w, sp.kw, sw)
+            else:
+                oh, ow, pt, pb, pl, pr = valid_out(h, sp.kh, sh), valid_out(w, sp.kw, sw), 0, 0, 0, 0
+            if oh <= 0 or ow <= 0:
+                raise ConfigError(f"layer {i}: depthwise kernel larger than its {h}x{w} input")
+            cm = shape.c * sp.mult
+            params = {"weight": (sp.kh, sp.kw, shape.c, sp.mult)}
+            if sp.bias:
+                params["bias"] = (cm,)
+            plans.append(LayerPlan(i, sp, shape, TensorShape(cm, (oh, ow)), (pt, pb, pl, pr), params))
         elif isinstance(sp, (PoolSpec, AvgPoolSpec)):
             if not shape.is_spatial:
                 raise ConfigError(f"layer {i}: pool after a connect layer (input is flat)")

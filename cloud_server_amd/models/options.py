@@ -13,6 +13,9 @@ CATALOG = {
     "param_init": {"options": ["全零", "正态分布", "Xavier"], "default": "全零"},
     "activation_method": {"options": ["Sigmoid", "ReLU"], "default": "ReLU"},
     "padding_method": {"options": ["SAME", "VALID"], "default": "SAME"},
+    # not in the reference's catalog (it only builds dense convolutions): the layer name of a
+    # convolution entry, ``conv`` or ``depthwise`` (filter [kh, kw, cout] or [kh, kw, multiplier])
+    "convolution_method": {"options": ["Standard", "Depthwise"], "default": "Standard"},
     # not in the reference's catalog (it only builds max pools): a pool entry's "mode"
     "pooling_method": {"options": ["Max", "Average"], "default": "Max"},
     # nor is this one (its only norm is BatchNorm): a norm entry's "mode"
@@ -29,6 +32,7 @@ DSL_TOKENS = {
     "全零": "zero", "正态分布": "norm", "Xavier": "xavier",
     "Sigmoid": "sigmoid", "ReLU": "relu",
     "SAME": "SAME", "VALID": "VALID",
+    "Standard": "conv", "Depthwise": "depthwise",
     "Max": "max", "Average": "avg",
     "Batch": "batch", "Layer": "layer", "Group": "group", "Instance": "instance",
 }

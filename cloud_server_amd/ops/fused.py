@@ -205,6 +205,21 @@ _SIGS = {
     "csa_gn_fwd": (I, [P, P, P, P, P, P, F, I, F, I, P]),
     "csa_gn_bwd": (I, [P, P, P, P, P, P, P, P, I, F, I, P]),
     "csa_gn_bwd_params": (I, [P, I, I, P, P, P]),
+    # depthwise convolution (depthwise_conv.hip),
+    # geom = {B, H, W, C, kh, kw, sh, sw, pad_top, pad_left, OH, OW, M}:
+    # (geom) / (geom) / (geom) / () / () / (geom) /
+    # (x, w, bias, y, geom, act, alpha, form, stream) /
+    # (x, w, y, dy, dx, slab, dw, db, geom, act, alpha, form, stream) /
+    # (slab, rows, geom, dw, db, stream)
+    "csa_dw_ok": (I, [P]),
+    "csa_dw_form": (I, [P]),
+    "csa_dw_bwd_form": (I, [P]),
+    "csa_dw_lds_floats": (I, []),
+    "csa_dw_max_rows": (I, []),
+    "csa_dw_slab_rows": (I, [P]),
+    "csa_dw_fwd": (I, [P, P, P, P, P, I, F, I, P]),
+    "csa_dw_bwd": (I, [P, P, P, P, P, P, P, P, P, I, F, I, P]),
+    "csa_dw_bwd_params": (I, [P, I, P, P, P, P]),
     # dropout with counter-RNG masks (dropout.hip; ops/dropout_ref.py is the definition)
     "csa_drop_fwd": (I, [P, P, L, L, L, L, U64, P, P, I, F, I, F, I, P]),
     "csa_drop_bwd": (I, [P, P, P, L, L, L, L, U64, P, I, F, I, F, P]),

@@ -193,6 +193,14 @@ class Buffers:
         hw = sh.hw[0] * sh.hw[1] if sh.is_spatial else 1
         return K.ints([self.B, hw, sh.c, lp.spec.groups])
 
+    def _dw_geom(self, lp: LayerPlan):
+        """{B, H, W, C, kh, kw, sh, sw, pad_top, pad_left, OH, OW, M} of a depthwise convolution."""
+        sp = lp.spec
+        h, w = lp.in_shape.hw
+        oh, ow = lp.out_shape.hw
+        return K.ints([self.B, h, w, lp.in_shape.c, sp.kh, sp.kw, sp.stride[0], sp.stride[1],
+                       lp.pads[0], lp.pads[2], oh, ow, sp.mult])
+
     @staticmethod
     def _bn_channels(u: Unit) -> int:
         """Channel count of a bn unit: C of an NHWC tensor, the features of a 2-D one."""
@@ -209,7 +217,7 @@ class Buffers:
             u.x = prev.y if prev is not None else None
             if prev is None and u.kind != "conv":
                 # first unit reads no raw images: materialise the gathered float input once
-                # per step (NHWC [B, 28, 28, 1] for a bn / pool / lrn / gn unit)
+                # per step (NHWC [B, 28, 28, 1] for a bn / pool / lrn / gn / dw unit)
                 self.x_dense_in = torch.zeros(B, u.layer.in_shape.numel, **f32)
                 ish = u.layer.in_shape
                 u.x = (self.x_dense_in if u.kind == "dense" or not ish.is_spatial
@@ -227,6 +235,15 @@ class Buffers:
                 if not fo:                       # (both stored whole every step: no zero regions)
                     u.gn_stat = torch.zeros(B, lp.spec.groups, 2, **f32)
                     u.gn_slab = torch.zeros(B, 2, lp.in_shape.c, **f32)
+            elif u.kind == "dw":
+                oh, ow = lp.out_shape.hw
+                u.y = torch.zeros(B, oh, ow, lp.out_shape.c, **f32)
+                if not fo:
+                    geom = self._dw_geom(lp)
+                    u.dw_form = int(self.lib.csa_dw_bwd_form(geom))
+                    if u.dw_form == 1:           # (every row stored whole every step: no zero regions)
+                        row = (lp.spec.kh * lp.spec.kw + 1) * lp.out_shape.c
+                        u.dw_slab = torch.zeros(int(self.lib.csa_dw_slab_rows(geom)), row, **f32)
             elif u.kind == "bn":
                 u.y = torch.zeros_like(u.x)
                 ch = self._bn_channels(u)

@@ -71,6 +71,20 @@ no zero regions.  The backward launch runs even when the unit is first (no input
 but the parameter gradients), then ``csa_gn_bwd_params`` stores them into the flat gradient.
 ``csa_gn_ok`` is asked at plan time.
 
+A depthwise convolution (``DepthwiseConvSpec``: ``{"layer": "depthwise"}``,
+``tf.nn.depthwise_conv2d``) is always a standalone ``dw`` unit (``depthwise_conv.hip``),
+forward-only programs included: it is not a ``ConvSpec``, so it never joins the pair, never
+fuses a pool and never becomes a gconv unit.  Pending norm / act layers are materialised in
+front of it; an ``active`` right behind it rides in the unit's launches (``Unit.act``) when its
+backward can be formed from y alone (``_y_ok``; a leaky alpha < 0 stays pending and is lowered
+where x is at hand), a pool behind it is a standalone ``pool`` unit and a norm behind it a
+standalone ``bn`` unit (``as_transform`` takes a norm only behind a ``conv`` unit).  The
+backward launch runs even when the unit is first (no input gradient, but the weight and bias
+gradients); it STORES them into the flat gradient, through a ``[R][(taps + 1) * C * M]`` slab
+of exclusive rows (``Unit.dw_slab``, every row stored whole every step: no zero regions) that
+``csa_dw_bwd_params`` folds in row order, or directly in the owner form.  No atomics: the
+deterministic program is the same launches.  ``csa_dw_ok`` is asked at plan time.
+
 ``options.augment`` adds one launch in front of the training step (``augment.hip``): this
 step's batch, warped for (seed, step, dataset row) as ops/augment_ref.py defines it, lands in
 ``aug_img`` and every training-time reader of the images takes that buffer (``_train_src``).
@@ -87,8 +101,8 @@ from typing import List, Optional
 
 import torch
 
-from ..models.dsl import (ActSpec, AvgPoolSpec, ConvSpec, DenseSpec, DropoutSpec, GroupNormSpec, LayerPlan, LrnSpec,
-                          NormSpec, PoolSpec)
+from ..models.dsl import (ActSpec, AvgPoolSpec, ConvSpec, DenseSpec, DepthwiseConvSpec, DropoutSpec, GroupNormSpec,
+                          LayerPlan, LrnSpec, NormSpec, PoolSpec)
 from ..ops import fused as K
 from ..utils.streams import dedicated_stream
 
@@ -173,9 +187,9 @@ class Transform:
 
 @dataclass
 class Unit:
-    kind: str                               # "conv" | "dense" | "gconv" | "bn" | "pool" | "drop" | "lrn" | "gn"
+    kind: str                               # "conv" | "dense" | "gconv" | "bn" | "pool" | "drop" | "lrn" | "gn" | "dw"
     layer: LayerPlan
-    act: Optional[ActSpec] = None           # conv: fused output act; bn / drop: applied first; gn: applied last
+    act: Optional[ActSpec] = None           # conv / dw: fused output act; bn / drop: applied first; gn: applied last
     pool: Optional[LayerPlan] = None        # conv: fused pool
     in_tf: Transform = field(default_factory=Transform)   # transform of this unit's INPUT
     x: Optional[torch.Tensor] = None        # input tensor (pre-transform), None = raw images
@@ -215,6 +229,9 @@ class Unit:
     # gn units (_alloc)
     gn_stat: Optional[torch.Tensor] = None  # the forward's {mean, rstd} per (sample, group), kept for the backward
     gn_slab: Optional[torch.Tensor] = None  # the backward's per-sample channel sums [B][2][C]
+    # dw units (_alloc)
+    dw_form: int = 0                        # the backward's form (1: split with a slab, 2: owner)
+    dw_slab: Optional[torch.Tensor] = None  # split form: exclusive partial rows [R][(taps + 1) * C * M]
 
 
 class Plan:
@@ -327,6 +344,10 @@ class Plan:
                 if self.lib.csa_gn_ok(self._gn_geom(lp)) != 1:
                     raise Unsupported(f"norm layer {lp.name}: batch x map x channels beyond the group-norm "
                                       f"kernels' 2^30 index range")
+            elif isinstance(lp.spec, DepthwiseConvSpec):
+                if self.lib.csa_dw_ok(self._dw_geom(lp)) != 1:
+                    raise Unsupported(f"depthwise layer {lp.name}: batch x map x channels or taps x channels "
+                                      f"beyond the depthwise kernels' 2^30 index range (65534 taps)")
 
         i = 0
         while i < len(layers):
@@ -383,6 +404,15 @@ class Plan:
                 act = nxt if isinstance(nxt, ActSpec) else None
                 _act_id(act)
                 units.append(Unit("gn", lp, act=act))
+                i += 2 if act is not None else 1
+            elif isinstance(sp, DepthwiseConvSpec):
+                # always a standalone unit, forward-only programs included; the activation right
+                # behind it rides in its launches when its backward can be formed from y alone
+                materialise()                    # dw(act(norm(x))): the transform first
+                nxt = layers[i + 1].spec if i + 1 < len(layers) else None
+                act = nxt if isinstance(nxt, ActSpec) and _y_ok(nxt) else None
+                _act_id(act)
+                units.append(Unit("dw", lp, act=act))
                 i += 2 if act is not None else 1
             elif isinstance(sp, DropoutSpec):
                 i += 1
@@ -730,6 +760,9 @@ class Plan:
         its own backward, ``csa_gn_bwd`` then ``csa_gn_bwd_params``, STORES the scale / offset
         gradients of that layer index before unit k's bucket is issued, and the activation that
         rides in the unit has no parameters — checked against the launches, the rule holds.)
+        (A depthwise convolution is a ``dw`` unit whose main layer is the layer itself: its own
+        backward, ``csa_dw_bwd`` then ``csa_dw_bwd_params`` in the split form, STORES the weight
+        and bias gradients of that layer index before unit k's bucket is issued.)
         Each time the ready suffix has grown by >= ``min_bucket`` bytes it is all-reduced
         on a side stream (captured into the same HIP graph) while the main stream keeps
         computing conv gradients; the optimizer waits for the side stream.  With the

@@ -306,7 +306,7 @@ class HipProgram(Plan, Buffers):
         if self.pair is not None and k < 2:
             if k == 1:
                 self._pair_bwd(st)
-        elif u.kind in ("bn", "pool", "drop", "lrn", "gn"):
+        elif u.kind in ("bn", "pool", "drop", "lrn", "gn", "dw"):
             self._standalone_bwd(u, prev, st)
         elif u.kind == "gconv":
             self._gconv_bwd(u, prev, st)
@@ -404,7 +404,7 @@ class HipProgram(Plan, Buffers):
         for k, u in enumerate(self.units):
             if self.pair is not None and k < 2:
                 continue
-            if u.kind in ("bn", "pool", "drop", "lrn", "gn"):
+            if u.kind in ("bn", "pool", "drop", "lrn", "gn", "dw"):
                 self._standalone_fwd(u, st)
                 continue
             if u.kind == "gconv":
@@ -528,6 +528,12 @@ class HipProgram(Plan, Buffers):
                                     K.ptr(u.y), K.ptr(stat), self._gn_geom(u.layer), float(u.layer.spec.epsilon),
                                     _act_id(u.act), _alpha(u.act), 0, st), "gn_fwd")
             return
+        if u.kind == "dw":
+            lp = u.layer
+            bias = self.views[f"{lp.name}.bias"] if lp.spec.bias else None
+            self._rc(lib.csa_dw_fwd(K.ptr(u.x), K.ptr(self.views[f"{lp.name}.weight"]), K.ptr(bias), K.ptr(u.y),
+                                    self._dw_geom(lp), _act_id(u.act), _alpha(u.act), 0, st), "dw_fwd")
+            return
         if u.kind == "pool" and isinstance(u.layer.spec, AvgPoolSpec):
             self._rc(lib.csa_avgpool_fwd(K.ptr(u.x), K.ptr(u.y), self._pool_geom_full(u), 0, st), "avgpool_fwd")
             return
@@ -598,6 +604,19 @@ class HipProgram(Plan, Buffers):
                                     self._gn_geom(u.layer), _act_id(u.act), _alpha(u.act), 0, st), "gn_bwd")
             self._rc(lib.csa_gn_bwd_params(K.ptr(u.gn_slab), self.B, u.layer.in_shape.c, K.ptr(G[f"{nm}.scale"]),
                                            K.ptr(G[f"{nm}.offset"]), st), "gn_bwd_params")
+            return
+        if u.kind == "dw":
+            # (a first unit has no input gradient and still has weight and bias gradients)
+            lp, G = u.layer, self.gviews
+            gw = G[f"{lp.name}.weight"]
+            gb = G[f"{lp.name}.bias"] if lp.spec.bias else None
+            geom = self._dw_geom(lp)
+            self._rc(lib.csa_dw_bwd(K.ptr(u.x), K.ptr(self.views[f"{lp.name}.weight"]), K.ptr(u.y), K.ptr(u.dy),
+                                    K.ptr(dx), K.ptr(u.dw_slab), K.ptr(gw), K.ptr(gb), geom, _act_id(u.act),
+                                    _alpha(u.act), u.dw_form, st), "dw_bwd")
+            if u.dw_form == 1:
+                self._rc(lib.csa_dw_bwd_params(K.ptr(u.dw_slab), u.dw_slab.shape[0], geom, K.ptr(gw), K.ptr(gb), st),
+                         "dw_bwd_params")
             return
         if u.kind == "pool" and isinstance(u.layer.spec, AvgPoolSpec):
             if dx is not None:
